@@ -66,10 +66,77 @@ def parse():
     ap.add_argument("--no-batch-sweep", action="store_true", help="skip the extra batch 1 / 8 measurements")
     ap.add_argument("--no-accuracy", action="store_true", help="skip the mAP@0.5-vs-reference leg on the committed mini split")
     ap.add_argument("--cpu-seconds", type=float, default=30.0, help="budget of the CPU baseline leg (the benchmark's batch always gets a warm-up + >= 3 timed passes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 "
+                         "(float64 for float64 / integer outputs), at most 64 MB in all: an output over its share is replaced by a "
+                         "fixed seeded sample of its rows, <name>_sample_rows.npy holding the row indices")
     args = ap.parse_args()
     if args.graph and args.workload != "detector_train":
         ap.error("--graph applies to --workload detector_train (the inference engines have their own MILLIEYE_GRAPH switch)")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     return args
+
+
+# The conv (tile, split_k) choices the engine's autotuner made on an MI355X for the layers of the default line (every leg).
+# Timed afresh in each process, close candidates come out differently from run to run, and with them the last bits of what
+# the layers compute (the output rows are ordered by confidence: near-equal rows then swap places), so two runs with the
+# same arguments would not compute the same outputs.  The benchmark runs this plan instead; layer shapes missing from it
+# are timed as before.  The library itself is untouched (every other caller keeps tuning per process and its private cache),
+# and MILLIEYE_TUNE_CACHE set by the caller wins.  Measured again with the tuner itself, on an MI355X:
+#     rm -f new.json; MILLIEYE_TUNE_CACHE=new.json python bench.py --no-cpu-baseline; mv new.json profiles/<this file>
+CONV_PLAN = os.path.join("profiles", "bench_conv_plan_v15_gfx950.json")   # (v15: engine._tune_file's kernel generation)
+
+
+def pin_conv_plan():
+    """Point the engine's tune file at a private copy of CONV_PLAN (the tuner writes back what it times for shapes missing
+    from it; the committed file stays as it is).  Returns the source, or None when the caller chose a tune file."""
+    import atexit
+    import shutil
+    import tempfile
+    if os.environ.get("MILLIEYE_TUNE_CACHE"):
+        return os.environ.get("BENCH_CONV_PLAN")   # (a rank started by spawn_ranks: its parent pinned the plan)
+    directory = tempfile.mkdtemp(prefix="millieye_bench_plan_")
+    atexit.register(shutil.rmtree, directory, True)
+    path = os.path.join(directory, "plan.json")
+    shutil.copy(os.path.join(ROOT, CONV_PLAN), path)
+    os.environ["MILLIEYE_TUNE_CACHE"] = path   # (inherited by the ranks spawn_ranks starts)
+    os.environ["BENCH_CONV_PLAN"] = CONV_PLAN
+    return CONV_PLAN
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+DUMP_SEED = 0
+
+
+def dump_outputs(directory, named):
+    """``--dump-outputs``: ``named`` (name -> tensor) as ``directory/<name>.npy``.  Floating outputs are stored as float32
+    (float64 stays float64), integer / bool ones as float64 (exact).  The 64 MB budget is split evenly over the outputs; one
+    over its share keeps a sample of its rows (last axis whole, row = every leading index): evenly spaced from an offset drawn
+    with a fixed seed, a function of the output's shape alone, so that two builds with the same arguments sample the same rows.  Returns a manifest."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = (DUMP_LIMIT_BYTES - 4096 * len(named)) // max(1, len(named))  # (4 KiB per file for the .npy headers)
+    manifest = {}
+    for name, t in named.items():
+        t = t.detach()
+        dtype = torch.float64 if t.dtype == torch.float64 or not t.is_floating_point() else torch.float32
+        t = t.to(dtype)
+        shape = list(t.shape)
+        item = 4 if dtype == torch.float32 else 8
+        entry = {"shape": shape, "dtype": str(dtype).replace("torch.", "")}
+        if t.numel() * item > share:
+            rows = t.reshape(-1, shape[-1]) if t.dim() >= 2 and shape[-1] * item <= share // 2 else t.reshape(-1, 1)
+            k = share // (rows.shape[1] * item + 8)  # (+ 8: the row's index in <name>_sample_rows.npy)
+            # k rows evenly spaced over the output from a seeded offset: the same rows for the same shape, O(k) host work
+            start = int(np.random.default_rng(DUMP_SEED).integers(rows.shape[0] // k))
+            idx = start + (np.arange(k, dtype=np.int64) * rows.shape[0]) // k
+            np.save(os.path.join(directory, name + "_sample_rows.npy"), idx.astype(np.float64))
+            t = rows[torch.from_numpy(idx).to(rows.device)]
+            entry["sample_rows"] = int(k)
+        np.save(os.path.join(directory, name + ".npy"), t.cpu().numpy())
+        manifest[name] = entry
+    return manifest
 
 
 def spawn_ranks(args):
@@ -430,7 +497,9 @@ def allreduce_bench(args, world, rank, dev):
             for pc in pieces:
                 dist.all_reduce(pc)
 
-    def timed(fn):
+    dumped = {}
+
+    def timed(fn, dump=False):
         for _ in range(args.warmup):
             fn()
             flat.fill_(1.0)
@@ -449,10 +518,12 @@ def allreduce_bench(args, world, rank, dev):
             t = torch.tensor([e], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             e = float(t.item())
+        if dump and args.dump_outputs and rank == 0:
+            dumped.update(dump_outputs(args.dump_outputs, {"bucket": flat}))
         flat.fill_(1.0)
         return e
 
-    e_flat, e_chunk = timed(one_flat), timed(chunked)
+    e_flat, e_chunk = timed(one_flat), timed(chunked, dump=True)
     if rank == 0:
         nbytes = n * 4
         gbs = lambda e: round(nbytes * args.steps / e / 1e9, 2) if have_pg and e > 0 else None  # noqa: E731
@@ -475,6 +546,8 @@ def allreduce_bench(args, world, rank, dev):
                          "traffic": None,
                          "note": "bus bandwidth per GPU against 7 xGMI links x 153 GB/s; meaningful for N > 1 only"},
         }
+        if dumped:
+            out["outputs_dumped"] = {"dir": args.dump_outputs, "files": dumped}
         print(json.dumps(out))
     if dist.is_initialized():
         dist.barrier()
@@ -623,6 +696,7 @@ def accuracy_leg(dev):
 
 def main():
     args = parse()
+    conv_plan = pin_conv_plan()
     world, rank, local = init_dist(args)
     dev = torch.device("cuda", local if world > 1 else 0)
 
@@ -845,8 +919,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    result = step()  # (the last timed step: what it returned is what --dump-outputs writes)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -855,6 +930,20 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    from millieye_amd import engine as _engine
+    shapes_timed = _engine._TUNE_STATS["measured"]   # conv layer shapes the autotuner had to time for the steps above (0: all from the plan)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything else runs a step: the outputs may live in buffers the next step reuses
+        if args.workload == "detector":
+            named = {"featuremap": result[0], "yolo_outputs": result[1]}
+        elif args.workload == "detector_train":
+            named = {"loss": last["loss"]} if args.graph else {"yolo_outputs": result, "loss": last["loss"]}
+        elif args.workload == "train":
+            named = {"rows": result, "loss": last["loss"]}
+        else:
+            named = {"rows": result}
+        dumped = dump_outputs(args.dump_outputs, {k: v for k, v in named.items() if v is not None})
+    del result
 
     # The same K steps once more in the opt-in bf16 storage mode (BASELINE configs[2] / [4] name bf16 / fp16 for their
     # shapes), reported beside - never instead of - the fp32 `value` above: same barrier + max-over-ranks protocol.
@@ -1027,6 +1116,7 @@ def main():
                 "rccl_ranks": dist.get_world_size() if dist.is_initialized() else 0,
                 "conv_gflop_per_frame": round(plan.conv_flops / batch / 1e9, 3),
                 "arena_mb": round(plan.arena_bytes / 2 ** 20, 1),
+                "conv_plan": {"table": conv_plan, "layer_shapes_timed_in_this_run": shapes_timed},
             },
             "roofline": {
                 "bound": "mfma",
@@ -1044,6 +1134,8 @@ def main():
                 "by_class": conv_roofline.by_class,
             },
         }
+        if dumped is not None:
+            out["outputs_dumped"] = {"dir": args.dump_outputs, "files": dumped}
         if sweep:
             out["batch_sweep"] = sweep
         if strong_leg is not None:

@@ -56,6 +56,26 @@ def test_bench_more_gpus_than_visible_fails_loudly(hip_lib):
     assert res.returncode != 0 and "visible" in (res.stderr + res.stdout)
 
 
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat(hip_lib, tmp_path):
+    """``--dump-outputs DIR``: the rows the last timed step returned, as float32, bit for bit the same in a second process with
+    the same arguments - the default workload (full pipeline, yolov3 416 x 416, batch 32; 3 timed steps, the extra legs off),
+    each run with an empty private tune cache of its own: the inputs are seeded and both runs take every conv choice of the
+    timed path from bench.py's pinned plan (none timed in the run) - and ``--steps`` is what ``ms_per_step`` divides by."""
+    import numpy as np
+    args = ["--workload", "full", "--no-batch-sweep"]
+    runs = [_bench(args + ["--dump-outputs", str(tmp_path / d)], {"XDG_CACHE_HOME": str(tmp_path / ("cache_" + d))})
+            for d in ("a", "b")]
+    for out in runs:
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+        assert out["config"]["batch_per_gpu"] == 32 and abs(out["value"] - 32e3 / out["ms_per_step"]) < 0.01 * out["value"]
+        assert out["outputs_dumped"]["files"]["rows"]["shape"][0] == out["config"]["output_rows_last_step"] > 0
+        assert out["config"]["conv_plan"] == {"table": "profiles/bench_conv_plan_v15_gfx950.json", "layer_shapes_timed_in_this_run": 0}
+    assert sorted(os.listdir(tmp_path / "a")) == ["rows.npy"]
+    a, b = np.load(tmp_path / "a" / "rows.npy"), np.load(tmp_path / "b" / "rows.npy")
+    assert a.dtype == np.float32 and a.shape[0] > 0 and np.isfinite(a).all()
+    assert a.shape == b.shape and np.array_equal(a, b), "two runs with the same arguments computed different rows"
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # data parallelism of the stage-3 step ON THE HIP PATH: two processes share the one leased GPU, each runs
 # Network.forward(..., targets) + loss.backward() through libmillieye_hip on its shard_batch() of one global batch and the

@@ -26,19 +26,23 @@ def test_cfg_emitters_parse_to_expected_graphs():
     assert tiny[1]["batch_normalize"] == "1"
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/module3_our_dataset"), reason="reference tree absent")
 def test_cfg_emitters_equal_reference_cfg_files():
+    """Against the reference's config/*.cfg files, parsed into tests/golden/reference_cfgs.json (make_golden.py --cfgs)."""
+    import json
+
     from millieye_amd.utils.parse_config import parse_model_config
     keys = ("type", "batch_normalize", "filters", "size", "stride", "activation", "layers", "from", "mask", "anchors",
             "classes")
+    with open(os.path.join(ROOT, "tests", "golden", "reference_cfgs.json")) as fh:
+        reference = json.load(fh)
 
     def norm(defs):
         return [{k: str(v).replace(" ", "") for k, v in d.items() if k in keys} for d in defs[1:]]
     for mine, ref in (("yolov3-tiny-12", "yolov3-tiny-12.cfg"), ("yolov3-tiny-coco", "yolov3-tiny-coco.cfg"),
                       ("yolov3", "yolov3.cfg")):
         a = norm(parse_model_config(ph.cfg_path(mine)))
-        b = norm(parse_model_config(os.path.join("/root/reference/module3_our_dataset/config", ref)))
-        assert a == b, mine
+        b = norm(reference[ref])
+        assert len(b) > 0 and a == b, mine
 
 
 def test_parse_data_config(tmp_path):
@@ -212,6 +216,82 @@ def test_bench_roi_stage_bytes_are_algorithmic():
                 if row.get("bound") == "hbm" and "algorithmic_bytes" in row and row["ms"] > 0:
                     gbs = row["algorithmic_bytes"] / (row["ms"] * 1e-3) / 1e9
                     assert row["frac"] <= gbs / bench.HBM_PEAK_GBS * 1.02 + 1e-4, (path, row)
+
+
+def test_bench_dump_outputs_budget_dtypes_and_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 / float64 files, the whole budget respected, an output over its share sampled by rows
+    with the same rows on every run (two builds are compared file for file)."""
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64 * 1024)
+    big = torch.from_numpy(synth.uniform("dump/big", (4, 500, 17)))
+    named = {"big": big, "flat": torch.from_numpy(synth.uniform("dump/flat", (40000,))),
+             "loss": torch.tensor(1.5, dtype=torch.float64), "count": torch.tensor([3, 2 ** 40]),
+             "half": torch.ones(5, 3, dtype=torch.bfloat16)}
+    man = bench.dump_outputs(str(tmp_path / "a"), named)
+    bench.dump_outputs(str(tmp_path / "b"), named)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["big.npy", "big_sample_rows.npy", "count.npy", "flat.npy", "flat_sample_rows.npy", "half.npy", "loss.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_LIMIT_BYTES
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    assert np.load(tmp_path / "a" / "count.npy").tolist() == [3.0, 2.0 ** 40]  # integers exact (float64)
+    assert np.load(tmp_path / "a" / "loss.npy").dtype == np.float64 and np.load(tmp_path / "a" / "half.npy").dtype == np.float32
+    rows = np.load(tmp_path / "a" / "big_sample_rows.npy").astype(np.int64)
+    sample = np.load(tmp_path / "a" / "big.npy")
+    assert man["big"]["shape"] == [4, 500, 17] and man["big"]["sample_rows"] == len(rows) == sample.shape[0] > 0
+    assert np.all(np.diff(rows) > 0) and np.array_equal(sample, big.reshape(-1, 17).numpy()[rows])
+    rows = np.load(tmp_path / "a" / "flat_sample_rows.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "flat.npy"), named["flat"].numpy()[rows, None])
+    assert "sample_rows" not in man["loss"] and np.array_equal(np.load(tmp_path / "a" / "half.npy"), np.ones((5, 3)))
+
+
+def test_bench_conv_plan_holds_choices_the_tuner_offers(monkeypatch):
+    """bench.py's pinned conv plan (profiles/bench_conv_plan_*.json): of the kernel generation the engine's tune file names,
+    keyed like the tuner's cache for the default line's layers (416 x 416; batches 32, 8, 1 and the accuracy leg's 2), every
+    (tile, split_k) one the tuner offers for a key of that storage type."""
+    import json
+    import re
+
+    import bench
+    from millieye_amd import engine
+    monkeypatch.delenv("MILLIEYE_TUNE_CACHE", raising=False)
+    version = re.fullmatch(r"conv_tune_(v\d+)\.json", os.path.basename(engine._tune_file())).group(1)
+    assert os.path.basename(bench.CONV_PLAN) == f"bench_conv_plan_{version}_gfx950.json", "plan of another kernel generation"
+    with open(os.path.join(ROOT, bench.CONV_PLAN)) as fh:
+        table = json.load(fh)
+    assert len(table) >= 30
+    f32_tiles = engine._TUNE_TILES + engine._TUNE_TILES_TAIL + engine._TUNE_TILES_P8_F32 + (50, 60)
+    h16_tiles = engine._TUNE_TILES_BF16 + engine._TUNE_TILES_P8 + (50, 60, 40, 41)
+    for k, (tile, split) in table.items():
+        key = tuple(int(x) for x in k.split(","))
+        assert len(key) in (9, 10) and key[0] in (1, 2, 8, 32) and key[3] > 4 and key[1] == key[2], k
+        half = len(key) == 10
+        assert tile in (h16_tiles if half else f32_tiles), (k, tile)
+        assert split in engine._TUNE_SPLITS, (k, split)
+        if tile in (50, 60) or tile >= 100 or (half and tile in (40, 41)):
+            assert split == 1, (k, tile, split)   # (kernels without a K split)
+        if not half and tile in engine._TUNE_TILES_TAIL:
+            assert split > 1, (k, tile, split)    # (tail tiles are offered with split_k >= 2 only)
+
+
+def test_bench_pins_its_conv_plan_in_a_private_copy(monkeypatch):
+    """bench.py runs the committed plan through a copy (the tuner writes back what it times; the committed file stays as it
+    is); a tune file the caller chose wins."""
+    import filecmp
+
+    import bench
+    monkeypatch.setenv("MILLIEYE_TUNE_CACHE", "")   # (unset for pin_conv_plan; setenv so that the teardown removes what it sets)
+    monkeypatch.setenv("BENCH_CONV_PLAN", "")
+    assert bench.pin_conv_plan() == bench.CONV_PLAN
+    path = os.environ["MILLIEYE_TUNE_CACHE"]
+    assert os.path.abspath(path) != os.path.join(ROOT, bench.CONV_PLAN)
+    assert filecmp.cmp(path, os.path.join(ROOT, bench.CONV_PLAN), shallow=False)
+    assert bench.pin_conv_plan() == bench.CONV_PLAN and os.environ["MILLIEYE_TUNE_CACHE"] == path   # (a spawned rank)
+    monkeypatch.setenv("MILLIEYE_TUNE_CACHE", "/elsewhere/mine.json")
+    monkeypatch.delenv("BENCH_CONV_PLAN")
+    assert bench.pin_conv_plan() is None and os.environ["MILLIEYE_TUNE_CACHE"] == "/elsewhere/mine.json"
 
 
 def test_head_caches_follow_replaced_inner_modules():
