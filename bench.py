@@ -15,8 +15,10 @@ Workloads (``--workload``):
             gradient bucket + Adam step, batch 8 per GPU                                  [BASELINE configs[3] shape]
   detector_train  Darknet.forward(x, targets) + HIP backward of every layer + full-gradient all-reduce + SGD
 ``--dtype bf16 | f16``: the opt-in 16-bit storage modes of the detector for the inference workloads and for the
-frozen detector of ``train``; e.g. ``--dtype f16 --size 608 --batch 16`` is the per-GPU shape of BASELINE configs[4].  The default
-fp32 line also carries the same steps re-run in bf16 storage as ``bf16_storage_mode`` (never as ``value``).
+frozen detector of ``train``; e.g. ``--dtype f16 --size 608 --batch 16`` is the per-GPU shape of BASELINE configs[4].
+``--full``: everything the headline figure does not need runs only with it - the same steps re-run in bf16 storage as
+``bf16_storage_mode`` (never as ``value``), the strong-scaling reading, the batch 1 / 8 sweep, the ``roofline`` and ``stages``
+tables, the CPU baseline and the accuracy leg.
 """
 import argparse
 import json
@@ -52,7 +54,7 @@ def parse():
     ap.add_argument("--prewarm-seconds", type=float, default=1.0, help="untimed clock ramp-up before the warmup")
     ap.add_argument("--scaling", default="weak", choices=("weak", "strong"),
                     help="weak (default): --batch frames PER GPU; strong: --batch frames in total, sharded over the ranks "
-                         "(parallel.shard_range).  An N > 1 weak run of an inference workload also times the strong reading "
+                         "(parallel.shard_range).  An N > 1 weak --full run of an inference workload also times the strong reading "
                          "and reports it as `strong_scaling` in the same line")
     ap.add_argument("--graph", action="store_true",
                     help="detector_train: forward + YOLO losses + backward as one captured hipGraph per step "
@@ -60,6 +62,11 @@ def parse():
     ap.add_argument("--no-prefetch", action="store_true",
                     help="train: do not run the frozen detector of the next batch under the current batch's tail "
                          "(Network.queue_detector_prefetch; A/B)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the extra legs: the bf16 storage line, the strong-scaling reading (N > 1), "
+                         "the batch 1 / 8 sweep, the per-launch and per-stage roofline tables, the CPU baseline and the "
+                         "mAP@0.5-vs-reference leg.  Off by default: a plain run sets up, warms up, times its steps, writes "
+                         "--dump-outputs and prints the headline line; the --no-* switches below opt out of single legs of --full")
     ap.add_argument("--no-strong-leg", action="store_true", help="N > 1 weak runs: skip the extra strong-scaling measurement")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-bf16-line", action="store_true", help="skip the extra bf16-storage-mode measurement")
@@ -84,7 +91,7 @@ def parse():
 # same arguments would not compute the same outputs.  The benchmark runs this plan instead; layer shapes missing from it
 # are timed as before.  The library itself is untouched (every other caller keeps tuning per process and its private cache),
 # and MILLIEYE_TUNE_CACHE set by the caller wins.  Measured again with the tuner itself, on an MI355X:
-#     rm -f new.json; MILLIEYE_TUNE_CACHE=new.json python bench.py --no-cpu-baseline; mv new.json profiles/<this file>
+#     rm -f new.json; MILLIEYE_TUNE_CACHE=new.json python bench.py --full --no-cpu-baseline; mv new.json profiles/<this file>
 CONV_PLAN = os.path.join("profiles", "bench_conv_plan_v15_gfx950.json")   # (v15: engine._tune_file's kernel generation)
 
 
@@ -796,7 +803,7 @@ def main():
         model = Darknet(cfg_path).eval()
         synth.fill_darknet_(model, "bench/" + args.cfg)
         synth.trained_like_(model, "bench/" + args.cfg + "/trained")
-        state_cpu = {k: v.clone() for k, v in model.state_dict().items()}
+        state_cpu = {k: v.clone() for k, v in model.state_dict().items()} if args.full else {}   # (the CPU baseline's weights)
         model = model.to(dev)
         net = None
 
@@ -809,7 +816,7 @@ def main():
         # class-0 logit clearly dominant (+3 vs -4) so that the class filter of Network.forward (class_idx 0,
         # my_models.py:462) keeps a realistic number of image proposals per frame with random backbone weights
         synth.fill_network_(net, "bench/" + args.cfg, cls0_bias=3.0, cls_bias=-4.0)
-        state_cpu = {k: v.clone() for k, v in net.state_dict().items()}
+        state_cpu = {k: v.clone() for k, v in net.state_dict().items()} if args.full else {}   # (the CPU baseline's weights)
         net = net.to(dev)
         model = net.base_detector
         if strong:
@@ -948,7 +955,7 @@ def main():
     # The same K steps once more in the opt-in bf16 storage mode (BASELINE configs[2] / [4] name bf16 / fp16 for their
     # shapes), reported beside - never instead of - the fp32 `value` above: same barrier + max-over-ranks protocol.
     alt = None
-    if args.dtype == "f32" and args.workload in ("full", "detector", "module2") and not args.no_bf16_line:
+    if args.full and args.dtype == "f32" and args.workload in ("full", "detector", "module2") and not args.no_bf16_line:
         try:
             model.compute_dtype = "bf16"
             t_alt = time.perf_counter() + 0.5
@@ -982,7 +989,7 @@ def main():
     # The other reading of "@batch32" on N GPUs: the metric's 32 frames in TOTAL, sharded over the ranks
     # (parallel.shard_range) - strong scaling - next to the weak line above (32 per GPU).  Same protocol, same K.
     strong_leg = None
-    if world > 1 and not strong and not args.no_strong_leg and args.dtype == "f32" \
+    if args.full and world > 1 and not strong and not args.no_strong_leg and args.dtype == "f32" \
             and args.workload in ("full", "detector", "module2") and batch >= world:
         try:
             lo, hi = par.shard_range(batch, rank, world)
@@ -1021,7 +1028,7 @@ def main():
     # and autotuning first), fp32 and bf16 storage, reported beside - never instead of - `value`
     os.environ["MILLIEYE_TUNE_SYNC"] = "0"  # from here on rank 0 plans alone (batch sweep, stage table, accuracy leg)
     sweep = []
-    if rank == 0 and args.workload in ("full", "detector") and args.dtype == "f32" and not args.no_batch_sweep:
+    if args.full and rank == 0 and args.workload in ("full", "detector") and args.dtype == "f32" and not args.no_batch_sweep:
         for b in (1, 8):
             if b >= batch:
                 continue
@@ -1067,7 +1074,7 @@ def main():
         torch.cuda.synchronize()
 
     det_passes = None
-    if args.workload == "detector_train":  # every rank (the step holds collectives when there is a process group)
+    if args.full and args.workload == "detector_train":  # every rank (the step holds collectives when there is a process group)
         from millieye_amd import detector_train as dtr
         det_passes = dtr.profile_step_passes(eager_step)   # (the passes' conv launches, sequential: an eager step also under --graph)
     if rank == 0:
@@ -1075,7 +1082,6 @@ def main():
         plan = model.engine_for(model.compute_dtype).plan_for(x)
         bf16 = args.dtype != "f32"
         peak = BF16_MFMA_PEAK_TFLOPS if bf16 else FP32_MFMA_PEAK_TFLOPS
-        ach, avg_us, launches, flops_per_launch, per_layer = conv_roofline(model, x, max(3, min(args.steps, 10)))
         out = {
             "metric": "frames/sec YOLOv3-416+fusion @batch32, 1/2/4/8 MI355X; mAP@0.5 vs ref",
             "value": round(frames / elapsed, 2),
@@ -1117,8 +1123,13 @@ def main():
                 "conv_gflop_per_frame": round(plan.conv_flops / batch / 1e9, 3),
                 "arena_mb": round(plan.arena_bytes / 2 ** 20, 1),
                 "conv_plan": {"table": conv_plan, "layer_shapes_timed_in_this_run": shapes_timed},
+                "full": bool(args.full),   # (the extra legs and tables below run only under --full)
             },
-            "roofline": {
+        }
+        per_layer = []
+        if args.full:   # per-launch timing of the plan's convolutions: steps of its own
+            ach, avg_us, launches, flops_per_launch, per_layer = conv_roofline(model, x, max(3, min(args.steps, 10)))
+            out["roofline"] = {
                 "bound": "mfma",
                 "kernel": (f"conv_igemm_buf_h16 (v_mfma_f32_32x32x16_{args.dtype} implicit-GEMM conv, all 3x3 / 1x1 layers)" if bf16
                            else "conv_igemm_buf_f32 (v_mfma_f32_32x32x2_f32 implicit-GEMM conv, all 3x3 / 1x1 layers)"),
@@ -1132,8 +1143,7 @@ def main():
                 "avg_launch_us": round(avg_us, 2),
                 "gflop_per_launch": round(flops_per_launch / 1e9, 3),
                 "by_class": conv_roofline.by_class,
-            },
-        }
+            }
         if dumped is not None:
             out["outputs_dumped"] = {"dir": args.dump_outputs, "files": dumped}
         if sweep:
@@ -1158,7 +1168,7 @@ def main():
                              "launches_per_step": alt["launches"], "avg_launch_us": round(alt["avg_us"], 2),
                              "by_class": alt.get("by_class")},
             }
-        if not args.no_cpu_baseline and world == 1 and args.workload not in ("train", "detector_train", "module2"):
+        if args.full and not args.no_cpu_baseline and world == 1 and args.workload not in ("train", "detector_train", "module2"):
             from millieye_amd.engine import pick_tap_module
             out["cpu_baseline"] = cpu_baseline(args, frames_cpu, state_cpu, cfgs.KNOWN[args.cfg](),
                                                pick_tap_module(model.module_defs), args.cpu_seconds, radar)
@@ -1187,29 +1197,29 @@ def main():
                    if ranks else "all-reduce skipped (1 rank, no process group), ") + "SGD), batch", 1).replace(
                 "Darknet.forward(x, targets) -> loss.backward() -> all-reduce -> SGD",
                 "Darknet.forward(x, targets) -> loss.backward()" + (" (+ overlapped all-reduce)" if ranks else "") + " -> SGD")
-            # this workload's own roofline: the convolution kernels of each pass, timed sequentially on one stream in one
-            # extra (untimed) step, against the matrix peak of the step's arithmetic type - not the forward kernel's inference figure
-            passes = det_passes
-            total_flops = sum(v[1] for v in passes.values())
-            # (the 16-bit step's three passes all run on the 16-bit matrix pipe since round 5: priced against ITS dense peak)
-            train_peak = FP32_MFMA_PEAK_TFLOPS if args.dtype == "f32" else BF16_MFMA_PEAK_TFLOPS
-            out["roofline"] = {
-                "bound": "mfma", "unit": "TFLOP/s", "peak": train_peak,
-                "kernel": "conv_igemm_buf_f32 (forward, data gradient) + conv_wgrad_* (weight gradient), fp32 MFMA" if args.dtype == "f32"
-                          else f"me_conv2d_h16 (forward, data gradient) + conv_wgrad_tile_h16_kernel (weight gradient), {args.dtype} MFMA "
-                               "(v_mfma_f32_32x32x16): batch-8 layers, 32 - 700 workgroups per launch",
-                "achieved": round(total_flops / (elapsed / args.steps) / 1e12, 2),
-                "frac": round(total_flops / (elapsed / args.steps) / 1e12 / train_peak, 4),
-                "note": "achieved / frac: conv FLOPs of the three passes over the WHOLE timed step (affine, pack, loss, SGD "
-                        "included); by_pass: each pass's conv launches alone, sequential",
-                "by_pass": {k: {"ms": round(ms, 3), "gflop": round(fl / 1e9, 1), "launches": cnt,
-                                "achieved": round(fl / ms / 1e9, 2), "frac": round(fl / ms / 1e9 / train_peak, 4)}
-                            for k, (ms, fl, cnt) in sorted(passes.items())},
-                # (per launch of the step's convolution kernels - forward, data gradient, weight gradient - from this workload's own
-                #  PMC passes: profiles/conv_traffic_detector_train_<dtype>[_graph].json)
-                "traffic": conv_traffic(args, batch, half=args.dtype != "f32")[0],
-                "traffic_source": conv_traffic(args, batch, half=args.dtype != "f32")[1],
-            }
+            if args.full:
+                # this workload's own roofline: the convolution kernels of each pass, timed sequentially on one stream in one
+                # extra (untimed) step, against the matrix peak of the step's arithmetic type - not the forward kernel's inference figure
+                total_flops = sum(v[1] for v in det_passes.values())
+                # (the 16-bit step's three passes all run on the 16-bit matrix pipe since round 5: priced against ITS dense peak)
+                train_peak = FP32_MFMA_PEAK_TFLOPS if args.dtype == "f32" else BF16_MFMA_PEAK_TFLOPS
+                out["roofline"] = {
+                    "bound": "mfma", "unit": "TFLOP/s", "peak": train_peak,
+                    "kernel": "conv_igemm_buf_f32 (forward, data gradient) + conv_wgrad_* (weight gradient), fp32 MFMA" if args.dtype == "f32"
+                              else f"me_conv2d_h16 (forward, data gradient) + conv_wgrad_tile_h16_kernel (weight gradient), {args.dtype} MFMA "
+                                   "(v_mfma_f32_32x32x16): batch-8 layers, 32 - 700 workgroups per launch",
+                    "achieved": round(total_flops / (elapsed / args.steps) / 1e12, 2),
+                    "frac": round(total_flops / (elapsed / args.steps) / 1e12 / train_peak, 4),
+                    "note": "achieved / frac: conv FLOPs of the three passes over the WHOLE timed step (affine, pack, loss, SGD "
+                            "included); by_pass: each pass's conv launches alone, sequential",
+                    "by_pass": {k: {"ms": round(ms, 3), "gflop": round(fl / 1e9, 1), "launches": cnt,
+                                    "achieved": round(fl / ms / 1e9, 2), "frac": round(fl / ms / 1e9 / train_peak, 4)}
+                                for k, (ms, fl, cnt) in sorted(det_passes.items())},
+                    # (per launch of the step's convolution kernels - forward, data gradient, weight gradient - from this workload's own
+                    #  PMC passes: profiles/conv_traffic_detector_train_<dtype>[_graph].json)
+                    "traffic": conv_traffic(args, batch, half=args.dtype != "f32")[0],
+                    "traffic_source": conv_traffic(args, batch, half=args.dtype != "f32")[1],
+                }
         if args.workload == "train":
             out["config"]["detector_prefetch"] = not args.no_prefetch
             if not args.no_prefetch:
@@ -1218,10 +1228,10 @@ def main():
             out["config"]["grad_bucket_bytes"] = int(last.get("bucket_bytes", 0))
             out["config"]["loss_last_step"] = round(float(last["loss"]), 5)
             out["config"]["workload"] = out["config"]["workload"].replace("inference", "training (heads), inference (detector)")
-        if args.workload in ("full", "detector"):
+        if args.full and args.workload in ("full", "detector"):
             rois = out["config"].get("rois_last_step", 0)
             out["stages"] = stage_roofline(model, net, x, step, rois)
-        if args.workload == "full" and not args.no_accuracy:
+        if args.full and args.workload == "full" and not args.no_accuracy:
             try:
                 out["accuracy"] = accuracy_leg(dev)
             except Exception as exc:  # never take the measurement down

@@ -76,6 +76,23 @@ def test_bench_dump_outputs_are_the_last_timed_step_and_repeat(hip_lib, tmp_path
     assert a.shape == b.shape and np.array_equal(a, b), "two runs with the same arguments computed different rows"
 
 
+def test_bench_plain_run_carries_the_headline_only(hip_lib):
+    """Without --full the benchmark stops after the timed steps: no bf16 re-run, batch sweep, roofline or stage tables, CPU
+    baseline or accuracy leg, and none of their opt-out switches is needed for that."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--prewarm-seconds", "0.1",
+           "--workload", "full", "--cfg", "yolov3-tiny-12", "--size", "160", "--batch", "4"]
+    res = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-4000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["value"] > 0 and out["unit"] == "frames/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert abs(out["value"] - 4e3 / out["ms_per_step"]) < 0.01 * out["value"] and out["config"]["full"] is False
+    for leg in ("bf16_storage_mode", "batch_sweep", "strong_scaling", "roofline", "stages", "cpu_baseline", "accuracy"):
+        assert leg not in out, leg
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # data parallelism of the stage-3 step ON THE HIP PATH: two processes share the one leased GPU, each runs
 # Network.forward(..., targets) + loss.backward() through libmillieye_hip on its shard_batch() of one global batch and the
@@ -394,14 +411,15 @@ def test_replicas_run_rank0s_tuned_plan(hip_lib, tmp_path):
 # ---------------------------------------------------------------------------------------------------------------------
 # the whole N = 2 flow of bench.py on the one leased GPU (BENCH_TEST_BACKEND=gloo: both ranks on GPU 0): self-launch, lock-step
 # pre-warm (the same number of untimed steps on every rank), rank 0's tuned plan on both replicas, barrier + max-over-ranks
-# timing, and - for the detector training step - the gradients leaving in chunks through GradChunkReducer every step
+# timing, and - for the detector training step - the gradients leaving in chunks through GradChunkReducer every step; under
+# --full, so that the strong-scaling reading and the per-pass roofline of the training step run too
 # ---------------------------------------------------------------------------------------------------------------------
 def _bench2(extra):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", BENCH_TEST_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--prewarm-seconds", "0.3",
-           "--no-cpu-baseline", "--no-bf16-line", "--no-accuracy", "--no-batch-sweep"] + extra
+           "--full", "--no-cpu-baseline", "--no-bf16-line", "--no-accuracy", "--no-batch-sweep"] + extra
     res = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-4000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

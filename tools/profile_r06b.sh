@@ -6,9 +6,9 @@
 TAG=r06; R=$PWD; OUT=$R/gpurun_out/prof; mkdir -p $OUT; export TMPDIR=/tmp
 export MILLIEYE_TUNE_CACHE=/tmp/tune_${TAG}b.json
 DATE=$(date +%Y-%m-%d)
-python bench.py --no-cpu-baseline --no-batch-sweep --no-accuracy --steps 3 --warmup 1 > /dev/null 2>&1   # tune both engines
+python bench.py --full --no-cpu-baseline --no-batch-sweep --no-accuracy --steps 3 --warmup 1 > /dev/null 2>&1   # tune both engines
 cd /tmp
-C32="python $R/bench.py --no-cpu-baseline --no-batch-sweep --no-accuracy --no-bf16-line --steps 3 --warmup 1 --prewarm-seconds 0.3"
+C32="python $R/bench.py --full --no-cpu-baseline --no-batch-sweep --no-accuracy --no-bf16-line --steps 3 --warmup 1 --prewarm-seconds 0.3"
 for dt in f32 bf16; do
   EXTRA=""; [ $dt = bf16 ] && EXTRA="--dtype bf16"
   MILLIEYE_BNECK=0 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d /tmp/pf_$dt -o f -- $C32 $EXTRA > /tmp/pf_$dt.log 2>&1
@@ -20,8 +20,8 @@ for dt in f32 bf16; do
 done
 cd $R
 cp $OUT/conv_traffic.json $OUT/conv_traffic_bf16.json $R/profiles/
-python bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench_full_b32.json 2> $OUT/${TAG}_bench_full_b32.err
-python bench.py --dtype bf16 --no-cpu-baseline --no-batch-sweep --steps 20 > $OUT/${TAG}_bf16_bench_full_b32.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 > $OUT/${TAG}_bench_full_b32.json 2> $OUT/${TAG}_bench_full_b32.err
+python bench.py --full --dtype bf16 --no-cpu-baseline --no-batch-sweep --steps 20 > $OUT/${TAG}_bf16_bench_full_b32.json 2>/dev/null
 python - <<'PY'
 import json
 for f in ("r06_bench_full_b32.json", "r06_bf16_bench_full_b32.json"):
@@ -37,7 +37,7 @@ PY
 python tools/memset_graph_probe.py 2>&1 | grep -v amdgpu.ids > $OUT/${TAG}_memset_graph_probe.txt
 (for m in philox cpu; do for p in 1 0; do M2_DROPOUT=$m python tools/m2_train_step.py 40 8 bf16 $p 2>&1 | grep "stage-2" | sed "s/\$/  [mask: $m]/"; done; done) > $OUT/${TAG}_m2_train_prefetch_ab.txt
 cd /tmp
-TR="python $R/bench.py --workload train --dtype bf16 --no-cpu-baseline --warmup 4"
+TR="python $R/bench.py --full --workload train --dtype bf16 --no-cpu-baseline --warmup 4"
 rocprofv3 --kernel-trace --stats -d /tmp/ts_a -o k -- $TR --steps 10 > /tmp/ts_a.log 2>&1
 rocprofv3 --kernel-trace --stats -d /tmp/ts_b -o k -- $TR --steps 50 > /tmp/ts_b.log 2>&1
 rocprofv3 --kernel-trace --stats -d /tmp/m2_a -o k -- python $R/tools/m2_train_step.py 10 8 bf16 1 > /tmp/m2_a.log 2>&1
