@@ -199,6 +199,12 @@ int me_yolo_decode_cand_f32(const me_yolo_desc* y, float conf_thresh, void* nms_
 int me_yolo_decode_cand_multi_f32(const me_yolo_desc* const* ys, int32_t count, float conf_thresh, void* nms_workspace,
                                   int32_t first, void* stream);
 int me_nms_batched_prepped_f32(const me_nms_desc* d, void* stream);
+/* me_nms_candidate_counts: after me_nms_batched_f32 / me_nms_batched_prepped_f32 (or the decodes that fill the lists) on
+ * `workspace` for [n, rows] predictions, cand_count[n] <- the number of rows of image i with objectness >= conf_thresh (the
+ * pre-NMS count `len(image_pred[image_pred[:, 4] >= conf_thres])` of module2_mixed/test_mixed.py:66-68) and fallback[n] <- 1
+ * where the image was redone by the single-workgroup kernel, else 0.  Either output may be NULL; device int32; stream-ordered. */
+int me_nms_candidate_counts(const void* workspace, int32_t n, int32_t rows, int32_t* cand_count, int32_t* fallback,
+                            void* stream);
 
 /* plain torchvision-style nms / batched_nms on explicit boxes (box_ops.* re-export used by
  *   run_sp.py:214 / run_mp.py:320).  boxes [m,4] xyxy, scores [m], labels [m] (float class ids,
@@ -597,6 +603,14 @@ int me_image_pad_resize_u8_f32(const uint8_t* src, int32_t h, int32_t w, float* 
  * mirrors the PADDED square left-right (horisontal_flip runs between pad_to_square and collate_fn's resize). */
 int me_image_pad_resize_flip_u8_f32(const uint8_t* src, int32_t h, int32_t w, float* dst, int32_t size, int32_t flip,
                                     void* stream);
+/* me_image_batch_pad_resize_flip_u8_f32: me_image_pad_resize_flip_u8_f32 for a ragged batch in ONE launch - replaces the
+ * per-frame ToTensor + pad_to_square + horisontal_flip + resize of module2_mixed/utils/datasets.py:275-304 (ExDarkDataset
+ * .__getitem__) and :322-324 (collate_fn's stack of resize).  src: every frame's uint8 HWC RGB bytes packed in one buffer of
+ * src_bytes bytes; desc [n,4] int64 on the device = (byte offset, h, w, flip) per frame; dst [n,3,size,size] float32 (16-byte
+ * aligned when size % 4 == 0).  Frame f of dst is bit-identical to me_image_pad_resize_flip_u8_f32 on that frame; a descriptor
+ * whose bytes do not lie inside src yields an all-zero frame. */
+int me_image_batch_pad_resize_flip_u8_f32(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int32_t n,
+                                          float* dst, int32_t size, void* stream);
 int me_radar_heatmap_f32(const double* points, const int32_t* offsets, const int32_t* sizes, int32_t n,
                          int32_t radar_maps_size, float* out, int32_t map_size, void* stream);
 

@@ -2,6 +2,9 @@
 // the CPU between the decoded jpg / radar pickle and the batch tensors Network.forward takes.
 //   me_image_pad_resize_u8_f32  ToTensor (u8 HWC -> f32 CHW / 255, datasets.py:203) + pad_to_square (:16-27, :211) +
 //                               resize(img, S) = F.interpolate(nearest) (:30-32, :317), one pass, one write.
+//   me_image_batch_pad_resize_flip_u8_f32
+//                               the same for a ragged batch (frames of different sizes packed in one uint8 buffer, one
+//                               descriptor per frame), one launch; with the stage-2 flip (module2_mixed/utils/datasets.py:275-304).
 //   me_radar_heatmap_f32        plot_radar_heatmap (:59-106: three np.histogram2d in float64, per-bin means, range
 //                               normalisation) + ToTensor().float() (:267) + pad_to_square (:270) +
 //                               F.interpolate(bilinear, align_corners=True) to the map size (:318-321).
@@ -46,6 +49,68 @@ __global__ __launch_bounds__(256) void image_pad_resize_kernel(const unsigned ch
     dst[idx] = r;
     dst[total + idx] = g;
     dst[2 * total + idx] = b;
+  }
+}
+
+// ---- ragged batch: every frame of a batch in one launch ------------------------------------------------------
+// grid (tiles, n): blockIdx.y = frame, each thread writes 4 consecutive output pixels of one row as float4 per channel
+// (S % 4 == 0; otherwise one pixel per thread).  Per pixel the index arithmetic, the division and the pad / flip rules are
+// those of image_pad_resize_kernel above, operation for operation: the two produce the same bits.
+constexpr int kBatchPix = 4 * 256;  // output pixels per workgroup and tile
+
+__global__ __launch_bounds__(256) void image_batch_pad_resize_kernel(const unsigned char* __restrict__ src,
+                                                                     long long src_bytes,
+                                                                     const long long* __restrict__ desc,
+                                                                     float* __restrict__ dst, int S) {
+  const int f = blockIdx.y;
+  const long long off = desc[4 * f];
+  const int h = (int)desc[4 * f + 1], w = (int)desc[4 * f + 2], flip = desc[4 * f + 3] != 0;
+  // a descriptor that does not lie inside the packed buffer reads nothing: the frame comes out as padding
+  const bool valid = h > 0 && w > 0 && off >= 0 && off + (long long)h * w * 3 <= src_bytes;
+  const int P = h > w ? h : w;
+  const int diff = h > w ? h - w : w - h;
+  const int pad1 = diff / 2;
+  const int pad_top = h <= w ? pad1 : 0, pad_left = h <= w ? 0 : pad1;
+  const float scale = (float)P / (float)S;
+  const int total = S * S;
+  const unsigned char* frame = src + (valid ? off : 0);
+  float* out = dst + (size_t)f * 3 * total;
+  auto pixel = [&](int y, int x, float& r, float& g, float& b) {
+    int py = P == S ? y : (int)floorf((float)y * scale);
+    int px = P == S ? x : (int)floorf((float)x * scale);
+    py = py < P - 1 ? py : P - 1;
+    px = px < P - 1 ? px : P - 1;
+    if (flip) px = P - 1 - px;
+    const int sy = py - pad_top, sx = px - pad_left;
+    r = 0.f, g = 0.f, b = 0.f;
+    if (valid && (unsigned)sy < (unsigned)h && (unsigned)sx < (unsigned)w) {
+      const unsigned char* p = frame + ((size_t)sy * w + sx) * 3;
+      r = (float)p[0] / 255.f;
+      g = (float)p[1] / 255.f;
+      b = (float)p[2] / 255.f;
+    }
+  };
+  if ((S & 3) == 0) {
+    for (int base = blockIdx.x * kBatchPix + threadIdx.x * 4; base < total; base += gridDim.x * kBatchPix) {
+      const int y = base / S, x0 = base - y * S;  // the 4 pixels share row y (S % 4 == 0, base % 4 == 0)
+      float4 r4, g4, b4;
+      pixel(y, x0, r4.x, g4.x, b4.x);
+      pixel(y, x0 + 1, r4.y, g4.y, b4.y);
+      pixel(y, x0 + 2, r4.z, g4.z, b4.z);
+      pixel(y, x0 + 3, r4.w, g4.w, b4.w);
+      *reinterpret_cast<float4*>(out + base) = r4;
+      *reinterpret_cast<float4*>(out + total + base) = g4;
+      *reinterpret_cast<float4*>(out + 2 * total + base) = b4;
+    }
+  } else {
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+      const int y = idx / S, x = idx - y * S;
+      float r, g, b;
+      pixel(y, x, r, g, b);
+      out[idx] = r;
+      out[total + idx] = g;
+      out[2 * total + idx] = b;
+    }
   }
 }
 
@@ -167,6 +232,22 @@ int me_image_pad_resize_flip_u8_f32(const uint8_t* src, int32_t h, int32_t w, fl
   hipLaunchKernelGGL(image_pad_resize_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, h, w, dst, size,
                      flip ? 1 : 0);
   return me::check_launch("image_pad_resize_kernel");
+}
+
+int me_image_batch_pad_resize_flip_u8_f32(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int32_t n,
+                                          float* dst, int32_t size, void* stream) {
+  if (n == 0) return 0;
+  ME_REQUIRE(src && desc && dst, ME_E_NULLPTR, "me_image_batch_pad_resize_flip_u8_f32: null pointer");
+  ME_REQUIRE(n > 0 && n <= 65535 && size > 0 && src_bytes > 0, ME_E_BADARG,
+             "me_image_batch_pad_resize_flip_u8_f32: bad n / size / src_bytes");
+  ME_REQUIRE((long long)size * size < (1ll << 30), ME_E_TOOBIG, "me_image_batch_pad_resize_flip_u8_f32: output too large");
+  ME_REQUIRE((size & 3) != 0 || me::aligned16(dst), ME_E_ALIGN, "me_image_batch_pad_resize_flip_u8_f32: dst not 16-byte aligned");
+  const int per_block = (size & 3) == 0 ? kBatchPix : 256;
+  int tiles = (int)me::ceil_div((int64_t)size * size, per_block);
+  if (tiles > 1024) tiles = 1024;
+  hipLaunchKernelGGL(image_batch_pad_resize_kernel, dim3(tiles, n), dim3(256), 0, (hipStream_t)stream, src,
+                     (long long)src_bytes, reinterpret_cast<const long long*>(desc), dst, size);
+  return me::check_launch("image_batch_pad_resize_kernel");
 }
 
 int me_radar_heatmap_f32(const double* points, const int32_t* offsets, const int32_t* sizes, int32_t n,

@@ -244,6 +244,15 @@ struct YoloCand {
 // spread over the whole chip.
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v);  // (DPP network, defined with the select kernel)
 
+// me_nms_candidate_counts: the per-image candidate counts (rows with objectness >= conf_thresh) and fallback flags a finished
+// pipeline left in its workspace, copied out for the caller (test_mixed's box_stat["before"], NMS diagnostics)
+__global__ __launch_bounds__(256) void copy_counts_kernel(NmsWs w, int n, int* __restrict__ cand, int* __restrict__ fallback) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  if (cand) cand[i] = w.cand_count[i];
+  if (fallback) fallback[i] = w.fallback[i];
+}
+
 __global__ __launch_bounds__(256) void zero_ints_kernel(int* p, int count) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < count) p[i] = 0;
@@ -1123,6 +1132,16 @@ extern "C" {
 int64_t me_nms_workspace_bytes(int32_t n, int32_t rows) {
   if (n <= 0 || rows <= 0) return 0;
   return ws_bytes(n, rows);
+}
+
+int me_nms_candidate_counts(const void* workspace, int32_t n, int32_t rows, int32_t* cand_count, int32_t* fallback,
+                            void* stream) {
+  ME_REQUIRE(workspace && (cand_count || fallback), ME_E_NULLPTR, "me_nms_candidate_counts: null pointer");
+  ME_REQUIRE(n > 0 && n <= 65535 && rows > 0 && rows <= MAX_ROWS, ME_E_BADARG, "me_nms_candidate_counts: bad n / rows");
+  ME_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, ME_E_ALIGN, "me_nms_candidate_counts: workspace alignment");
+  NmsWs w = carve(const_cast<void*>(workspace), n, rows);
+  hipLaunchKernelGGL(copy_counts_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, n, cand_count, fallback);
+  return me::check_launch("copy_counts_kernel");
 }
 
 static int nms_batched(const me_nms_desc* d, void* stream_, int prepped);

@@ -175,6 +175,8 @@ SIGNATURES = {
     "me_image_pad_resize_u8_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "me_image_pad_resize_flip_u8_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                                   C.c_void_p]),
+    "me_image_batch_pad_resize_flip_u8_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                                        C.c_void_p]),
     "me_radar_heatmap_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                        C.c_void_p]),
     "me_conv2d_f32": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
@@ -202,6 +204,7 @@ SIGNATURES = {
                                       C.c_int32, C.c_void_p]),
     "me_yolo_decode_f32": (C.c_int, [C.POINTER(YoloDesc), C.c_void_p]),
     "me_nms_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "me_nms_candidate_counts": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "me_nms_batched_f32": (C.c_int, [C.POINTER(NmsDesc), C.c_void_p]),
     "me_nms_boxes_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -27,7 +27,7 @@ from torch.utils.data import Dataset
 
 from .. import hip
 
-__all__ = ["MyDataset", "StagedImages", "StagedRadarMaps", "obtain_bboxs"]
+__all__ = ["MyDataset", "StagedImages", "StagedRaggedImages", "StagedRadarMaps", "obtain_bboxs"]
 
 _SCENES = ["0", "1", "2", "3", "4"]
 
@@ -118,6 +118,48 @@ class StagedImages:
             hip.check(lib.me_image_pad_resize_flip_u8_f32(d.data_ptr(), h, w, out[i].data_ptr(), self.size,
                                                           int(self.flips[i]), stream), "me_image_pad_resize_flip_u8_f32")
         return out
+
+
+class StagedRaggedImages(StagedImages):
+    """A ``StagedImages`` whose ``.to(device)`` builds the whole batch in one launch: every frame's bytes are packed into one
+    pinned uint8 buffer and uploaded once, with a ``[n,4]`` int64 descriptor ``(byte offset, h, w, flip)`` per frame, and
+    ``me_image_batch_pad_resize_flip_u8_f32`` writes ``[n,3,size,size]`` (bit-identical to the per-frame kernel).  ``.type()``
+    accepts the CUDA float tensor types, for callers that write ``imgs.type(torch.cuda.FloatTensor)``."""
+
+    def to(self, device, *_, **__):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise hip.MeError("StagedRaggedImages.to(): the batch is assembled by the HIP library - CUDA device required")
+        n = len(self.frames)
+        out = torch.empty(tuple(self.shape), device=device, dtype=torch.float32)
+        if n == 0:
+            return out
+        desc = torch.empty((n, 4), dtype=torch.int64)
+        total = 0
+        for i, frame in enumerate(self.frames):
+            h, w, c = frame.shape
+            if c != 3 or frame.dtype != torch.uint8 or h <= 0 or w <= 0:
+                raise hip.MeError(f"frame {i}: expected uint8 [h,w,3], got {frame.dtype} {tuple(frame.shape)}")
+            desc[i, 0], desc[i, 1], desc[i, 2], desc[i, 3] = total, h, w, int(self.flips[i])
+            total += h * w * 3
+        packed = torch.empty((total,), dtype=torch.uint8, pin_memory=True)
+        for i, frame in enumerate(self.frames):
+            start = int(desc[i, 0])
+            packed[start:start + frame.numel()].copy_(frame.reshape(-1))
+        d_src = packed.to(device, non_blocking=True)
+        d_desc = desc.pin_memory().to(device, non_blocking=True)
+        hip.check(hip.lib().me_image_batch_pad_resize_flip_u8_f32(d_src.data_ptr(), total, d_desc.data_ptr(), n,
+                                                                   out.data_ptr(), self.size, hip.stream_ptr()),
+                  "me_image_batch_pad_resize_flip_u8_f32")
+        return out
+
+    def type(self, dtype=None, non_blocking=False, **__):
+        if dtype is None:
+            return "torch.cuda.FloatTensor"
+        name = dtype if isinstance(dtype, str) else f"{getattr(dtype, '__module__', '')}.{getattr(dtype, '__name__', '')}"
+        if name != "torch.cuda.FloatTensor":
+            raise hip.MeError(f"StagedRaggedImages.type({dtype!r}): the batch is built on the GPU as torch.cuda.FloatTensor")
+        return self.to("cuda")
 
 
 class StagedRadarMaps:
