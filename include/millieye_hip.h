@@ -614,6 +614,75 @@ int me_image_batch_pad_resize_flip_u8_f32(const uint8_t* src, int64_t src_bytes,
 int me_radar_heatmap_f32(const double* points, const int32_t* offsets, const int32_t* sizes, int32_t n,
                          int32_t radar_maps_size, float* out, int32_t map_size, void* stream);
 
+/* ---- multi-stream front of the live demos (csrc/radar.hip) ----------------------------------
+ * me_radar_proposals_f64: the per-frame radar proposal chain of module3_our_dataset/run_mp.py:65-135 (= run_sp.py:117-175)
+ *   for `streams` independent camera + radar nodes in two launches (one workgroup per stream, then a packing pass):
+ *   from_3d_to_2d + projection_xyr_to_uv (data_collection/utils/utils.py:81-120), the FOV / depth / velocity filter
+ *   (run_mp.py:83), radar_dbscan (data_collection/utils/tracking.py:6-41; min_samples = 2: connected components of
+ *   `distance <= eps`), associate_clusters (:45-92; exact rectangular assignment by shortest augmenting paths),
+ *   KalmanBoxTracker / Tracker.update (:96-238; filterpy's predict / Joseph-form update restated, gain through the 7x7 inverse), the box
+ *   proposals (run_mp.py:93-109) and their normalisation for Network.forward (run_mp.py:119-135).  float64 wherever the
+ *   reference computes in float64, float32 where it stores into the cluster dtype (run_mp.py:285-286).
+ *   points [total,4] float64 rows (x, y, z, v) of every stream back to back (the radar frames a stream overlays, in order),
+ *   offsets [streams+1]; calib [streams,12] (fx cx fy cy k1 k2 t1 t2 k3 tx ty tz); image_size [streams,2] = (width, height)
+ *   of the FOV filter; frame_size [streams,2] = (w, h) of the camera frame the boxes are padded / normalised for.
+ *   state: me_radar_tracker_state_bytes(streams) bytes, 16-byte aligned, zero = no tracks (me_radar_tracker_reset).
+ *   Per-stream outputs (slot s of each): cloud_slots [streams, MAX_POINTS, 4] float64 (u, v, range, velocity) of the kept
+ *   points; labels [streams, MAX_POINTS] DBSCAN labels (-1 noise; may be NULL); clusters / tracked [streams, MAX_*, 8] 32-byte
+ *   records (uint32 num_points, float center[3], size[3], avgV) - the fresh clusters after the num_pts filter and the confirmed
+ *   live tracks; matches [streams, MAX_TRACKS] = the new-cluster index assigned to each track of the previous step or -1 (may
+ *   be NULL); proposals [streams, MAX_TRACKS, 4] float64 pixel boxes; counts [streams, 8] int32 = (status, kept points,
+ *   clusters, tracked, network boxes, live tracks, frame_count, pixel proposals).
+ *   Packed outputs: boxes [2 * streams * MAX_TRACKS, 5] float32: the first totals[0] rows are (stream, x1, y1, x2, y2)
+ *   stream-major - the radar_boxes_location of Network.forward - the second half is the launch's scratch; cloud [streams * MAX_POINTS, 4] + cloud_offsets [streams+1] - the (points,
+ *   offsets) of me_radar_heatmap_f32; totals [2] = (boxes, points).
+ *   A stream that exceeds a capacity gets status ME_RADAR_E_* , all-zero counts and an UNCHANGED state; the call returns 0.
+ * me_frame_means_f32: means[f] = mean of the elems_per_frame floats of frame f (double accumulation, fixed order) - the
+ *   img.mean() of the demos' auto mode (run_mp.py:204-212) for a whole batch. */
+#define ME_RADAR_MAX_POINTS 256
+#define ME_RADAR_MAX_CLUSTERS 32
+#define ME_RADAR_MAX_TRACKS 32
+#define ME_RADAR_COUNT_COLS 8
+#define ME_RADAR_OK 0
+#define ME_RADAR_E_POINTS 1   /* more than ME_RADAR_MAX_POINTS points pass the filter            */
+#define ME_RADAR_E_CLUSTERS 2 /* more than ME_RADAR_MAX_CLUSTERS clusters pass the num_pts filter */
+#define ME_RADAR_E_TRACKS 3   /* old tracks + unmatched clusters exceed ME_RADAR_MAX_TRACKS       */
+#define ME_RADAR_E_COST 4     /* the association cost is not finite (scipy raises ValueError)     */
+typedef struct me_radar_desc {
+  const double* points;
+  const int32_t* offsets;
+  const double* calib;
+  const int32_t* image_size;
+  const int32_t* frame_size;
+  void* state;
+  double* cloud_slots;
+  int32_t* labels;     /* may be NULL */
+  void* clusters;
+  void* tracked;
+  int32_t* matches;    /* may be NULL */
+  double* proposals;
+  int32_t* counts;
+  float* boxes;
+  double* cloud;
+  int32_t* cloud_offsets;
+  int32_t* totals;
+  double dt;           /* 1 / radar_fps */
+  double eps;          /* dbscan_eps */
+  double weights[4];   /* dbscan_weights */
+  double min_velocity, max_size, max_depth;
+  int32_t streams, max_age, min_hits, num_pts_filter;
+} me_radar_desc;
+/* the constants a binding sizes its buffers and reads the state with: which = 0 MAX_POINTS, 1 MAX_CLUSTERS, 2 MAX_TRACKS,
+ * 3 COUNT_COLS, 4 bytes of a stream's state header (int32 frame_count, int32 live tracks, padding), 5 bytes of one track
+ * (double x[9], double P[81], the 32-byte cluster record, int32 time_since_update, hit_streak, prev_hit_streak, padding);
+ * -1 otherwise.  A stream's state is the header followed by MAX_TRACKS tracks. */
+int32_t me_radar_capacity(int32_t which);
+int64_t me_radar_tracker_state_bytes(int32_t streams);
+/* zero the tracker state of one stream (which >= 0) or of all of them (which < 0); stream-ordered */
+int me_radar_tracker_reset(void* state, int32_t streams, int32_t which, void* stream);
+int me_radar_proposals_f64(const me_radar_desc* d, void* stream);
+int me_frame_means_f32(const float* imgs, int32_t n, int64_t elems_per_frame, float* means, void* stream);
+
 /* ---- evaluation tail -----------------------------------------------------------------
  * get_batch_statistics (module3_our_dataset/utils/utils.py:185-236) for one batch, on the output rows of
  * Network.forward as they are: rows [m,cols] = (image_i, x1,y1,x2,y2, ..., class_pred last), targets [q,6] =
@@ -739,7 +808,7 @@ int me_adam_step_f32(const me_adam_desc* d, void* stream);
 int32_t me_adam_chunk(void);
 
 /* sizes of the descriptor structs, so a binding can assert its mirror layout */
-int32_t me_sizeof(int32_t which); /* 0 conv, 1 pool, 2 yolo, 3 nms, 4 heads, 5 heads_weights, 6 conv16, 7 pack, 8 bneck16, 9 adam */
+int32_t me_sizeof(int32_t which); /* 0 conv, 1 pool, 2 yolo, 3 nms, 4 heads, 5 heads_weights, 6 conv16, 7 pack, 8 bneck16, 9 adam, 10 radar */
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,10 @@ serial-port capture, OpenCV window).  ``millieye_amd/pi
     mode: auto = fusion iff img.mean() < 0.08, else camera only                            (run_mp.py:204-212)
     Network.forward(img, radar_map, radar_box, mode)[:, 1:] -> batched_nms(.., 0.3) -> rescale_boxes to the frame
 
+:class:`MultiStreamFuser` is the same step for S camera + radar nodes behind one card: the radar chain of every stream on the
+device (``radar_proposals.DeviceRadarProposals``), one ragged-batch launch for the frames, one heat-map launch from the device
+cloud, per-frame means for the mode rule and at most two ``Network.forward`` calls (the fusion frames, the camera-only frames).
+
 Parity: every numeric stage is one of the pinned pieces (input kernels: tests/golden/dataset_small; Network.forward:
 network_*.npz; NMS: nms_synth; radar proposals: radar_proposals_synth + the unpinned Kalman part); the glue in this file
 restates run_mp's inline code and has no fixture of its own.
@@ -19,11 +23,11 @@ import numpy as np
 import torch
 
 from . import hip
-from .radar_proposals import RadarProposalGenerator
-from .utils.datasets import StagedImages, StagedRadarMaps, _pad_amounts
+from .radar_proposals import DeviceRadarProposals, RadarProposalGenerator
+from .utils.datasets import StagedImages, StagedRadarMaps, StagedRaggedImages, _pad_amounts
 from .utils.utils import box_ops, rescale_boxes
 
-__all__ = ["mode_selection", "radar_boxes_for_network", "FrameFuser"]
+__all__ = ["mode_selection", "radar_boxes_for_network", "FrameFuser", "MultiStreamFuser"]
 
 
 def mode_selection(mode, img, dark_threshold=0.08):
@@ -97,3 +101,100 @@ class FrameFuser:
             rescale_boxes(rows, self.img_size, (h, w))
         return rows, dict(mode=mode, proposals=payload["proposals"], radar_boxes=int(radar_box.shape[0]),
                           points=payload["points"])
+
+
+class MultiStreamFuser:
+    """:class:`FrameFuser` for ``streams`` camera + radar nodes in one step: ``fuser(frames, radar_frames)`` takes S uint8
+    ``[h,w,3]`` frames (sizes may differ per stream) and S lists of radar frames and returns a list of S ``(rows [m,7], info)``
+    with the meaning :class:`FrameFuser` gives them.  Stream ``s`` sees what its own ``FrameFuser`` would see; every stream
+    keeps its own tracker state on the device (``generator.reset(stream)`` forgets one).
+
+    Per step: one upload + two launches for the radar chain, one ragged-batch launch for the frames, one heat-map launch, one
+    launch for the per-frame means (auto mode), ``Network.forward`` once for the frames that select fusion and once for the
+    camera-only ones, the second NMS of every stream queued back to back, ``rescale_boxes`` per stream on the host rows.
+
+    The second NMS is one ``me_nms_boxes_f32`` call per stream, not one call with the label ``stream * num_classes + class``:
+    that entry point separates labels with torchvision's offset trick (``boxes + label * (max + 1)`` in float32), not by
+    equality, so a joint call would round the boxes of the later streams differently from the per-frame call of the demos."""
+
+    def __init__(self, model, calib_params, streams, model_mode=3, img_size=416, nms_iou=0.3, dark_threshold=0.08,
+                 **generator_kwargs):
+        self.model, self.model_mode, self.img_size, self.streams = model, model_mode, img_size, int(streams)
+        self.nms_iou, self.dark_threshold = nms_iou, dark_threshold
+        self.device = getattr(model, "device", None) or hip.default_device()
+        self.generator = DeviceRadarProposals(calib_params, streams, device=self.device, **generator_kwargs)
+
+    def __call__(self, frames, radar_frames):
+        return self.infer(self.prepare(frames, radar_frames))
+
+    def prepare(self, frames, radar_frames):
+        """Host half: checks and stages the raw frame bytes and radar frames (picklable; the trackers live on the device, so
+        the radar chain itself belongs to :meth:`infer`)."""
+        if len(frames) != self.streams or len(radar_frames) != self.streams:
+            raise hip.MeError(f"MultiStreamFuser: {len(frames)} frames / {len(radar_frames)} radar lists for {self.streams} streams")
+        frames = [torch.as_tensor(f) for f in frames]
+        for i, frame in enumerate(frames):
+            if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3:
+                raise hip.MeError(f"stream {i}: frame must be uint8 [h,w,3] (got {frame.dtype} {tuple(frame.shape)})")
+        return dict(hw=[(int(f.shape[0]), int(f.shape[1])) for f in frames], img=StagedRaggedImages(frames, self.img_size),
+                    radar_frames=[list(r) for r in radar_frames])
+
+    def _modes(self, img):
+        if self.model_mode != 3:
+            return [mode_selection(self.model_mode, None)] * self.streams
+        means = hip.frame_means(img).cpu()   # one launch, one copy of S floats
+        return [0 if float(m) < self.dark_threshold else 1 for m in means]
+
+    def infer(self, payload):
+        """Device half: radar chain, input kernels, mode selection, ``Network.forward`` per mode, second NMS, rescale."""
+        dev, n = self.device, self.streams
+        hws = payload["hw"]
+        img = payload["img"].to(dev)
+        step = self.generator.gen(payload["radar_frames"], hws)
+        radar_map = self.generator.heatmaps(32)   # the raw 32 x 32 maps, like FrameFuser (quirk q15)
+        counts = step.host_counts
+        modes = self._modes(img)
+        box_start = np.concatenate([[0], np.cumsum(counts[:, 4])])
+        outs = []
+        with torch.no_grad():
+            for mode in sorted(set(modes), key=lambda m: (m is None, m)):
+                idx = [s for s in range(n) if modes[s] == mode]
+                if len(idx) == n:
+                    rows = self.model(img, radar_map, step.radar_box, mode)
+                else:   # gather the sub-batch; the frame index column goes local and comes back as the stream number
+                    where = torch.tensor(idx, dtype=torch.int64).to(dev)
+                    box_rows = [r for s in idx for r in range(int(box_start[s]), int(box_start[s + 1]))]
+                    local = [float(k) for k, s in enumerate(idx) for _ in range(int(counts[s, 4]))]
+                    rb = step.radar_box[torch.tensor(box_rows, dtype=torch.int64).to(dev)]
+                    if len(local):
+                        rb[:, 0] = torch.tensor(local, dtype=torch.float32).to(dev)
+                    rows = self.model(img[where], radar_map[where], rb, mode)
+                    rows = torch.cat([where[rows[:, 0].long()].to(rows.dtype)[:, None], rows[:, 1:]], 1)
+                outs.append(rows)
+            rows = torch.cat(outs, 0) if len(outs) > 1 else outs[0]
+            per_stream = self._second_nms(rows)
+        proposals = self.generator._proposals.cpu().numpy()
+        result = []
+        for s in range(n):
+            r = per_stream[s]
+            if len(r):
+                rescale_boxes(r, self.img_size, hws[s])
+            result.append((r, dict(mode=modes[s], proposals=proposals[s, :int(counts[s, 7])].copy(),
+                                   radar_boxes=int(counts[s, 4]), points=int(counts[s, 1]))))
+        return result
+
+    def _second_nms(self, rows):
+        """``box_ops.batched_nms(rows[:, :4], rows[:, 4], rows[:, 6], nms_iou)`` of every stream's rows (stream = column 0 of
+        ``rows`` [m,8]): the rows are grouped by stream on the device (stable: each stream keeps the network's order), copied
+        once, the S calls are queued back to back on the grouped rows and their kept indices come back in one copy."""
+        n, dev = self.streams, rows.device
+        empty = torch.zeros((0, 7))
+        if rows.shape[0] == 0:
+            return [empty.clone() for _ in range(n)]
+        order = torch.sort(rows[:, 0], stable=True).indices
+        grouped = rows[order].to(torch.float32)
+        boxes, scores, labels = grouped[:, 1:5].contiguous(), grouped[:, 5].contiguous(), grouped[:, 7].contiguous()
+        host = grouped.cpu()
+        per = torch.bincount(host[:, 0].long(), minlength=n).tolist()
+        kept = hip.nms_indices_grouped(boxes, scores, labels, per, self.nms_iou)
+        return [host[k][:, 1:].clone() if per[s] else empty.clone() for s, k in enumerate(kept)]

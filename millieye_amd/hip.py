@@ -143,6 +143,24 @@ class Bneck16Desc(C.Structure):
     ]
 
 
+class RadarDesc(C.Structure):
+    """me_radar_desc: the multi-stream radar proposal chain (csrc/radar.hip)."""
+    _fields_ = [(name, C.c_void_p) for name in (
+        "points", "offsets", "calib", "image_size", "frame_size", "state", "cloud_slots", "labels", "clusters", "tracked",
+        "matches", "proposals", "counts", "boxes", "cloud", "cloud_offsets", "totals")] + [
+        ("dt", C.c_double), ("eps", C.c_double), ("weights", C.c_double * 4),
+        ("min_velocity", C.c_double), ("max_size", C.c_double), ("max_depth", C.c_double),
+        ("streams", C.c_int32), ("max_age", C.c_int32), ("min_hits", C.c_int32), ("num_pts_filter", C.c_int32),
+    ]
+
+
+# capacities / status words of me_radar_proposals_f64 (include/millieye_hip.h) and the layout of its tracker state;
+# load() checks every one of them against the library (me_radar_capacity)
+RADAR_MAX_POINTS, RADAR_MAX_CLUSTERS, RADAR_MAX_TRACKS, RADAR_COUNT_COLS = 256, 32, 32, 8
+RADAR_STATE_HEADER_BYTES, RADAR_TRACK_BYTES = 64, 768
+RADAR_STATUS = {1: ("points that pass the filter", RADAR_MAX_POINTS), 2: ("clusters", RADAR_MAX_CLUSTERS),
+                3: ("tracks", RADAR_MAX_TRACKS), 4: ("finite association costs", 0)}
+
 ADAM_MAX_TENSORS = 64
 
 
@@ -160,7 +178,7 @@ class AdamDesc(C.Structure):
 
 
 _STRUCTS = {0: ConvDesc, 1: PoolDesc, 2: YoloDesc, 3: NmsDesc, 4: HeadsDesc, 5: HeadsWeights, 6: Conv16Desc, 7: PackDesc,
-            8: Bneck16Desc, 9: AdamDesc}
+            8: Bneck16Desc, 9: AdamDesc, 10: RadarDesc}
 
 # name -> (restype, argtypes); every symbol include/millieye_hip.h declares
 SIGNATURES = {
@@ -179,6 +197,11 @@ SIGNATURES = {
                                                         C.c_void_p]),
     "me_radar_heatmap_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                        C.c_void_p]),
+    "me_radar_capacity": (C.c_int32, [C.c_int32]),
+    "me_radar_tracker_state_bytes": (C.c_int64, [C.c_int32]),
+    "me_radar_tracker_reset": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "me_radar_proposals_f64": (C.c_int, [C.POINTER(RadarDesc), C.c_void_p]),
+    "me_frame_means_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
     "me_conv2d_f32": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
     "me_conv2d_flops": (C.c_int64, [C.POINTER(ConvDesc)]),
     "me_conv2d_workspace_bytes": (C.c_int64, [C.POINTER(ConvDesc)]),
@@ -332,6 +355,11 @@ def load(path=None):
         if lib_.me_sizeof(which) != C.sizeof(struct):
             raise MeError(f"struct layout mismatch for {struct.__name__}: C {lib_.me_sizeof(which)} vs "
                           f"ctypes {C.sizeof(struct)}")
+    radar = (RADAR_MAX_POINTS, RADAR_MAX_CLUSTERS, RADAR_MAX_TRACKS, RADAR_COUNT_COLS, RADAR_STATE_HEADER_BYTES,
+             RADAR_TRACK_BYTES)
+    got = tuple(lib_.me_radar_capacity(i) for i in range(len(radar)))
+    if got != radar or lib_.me_radar_tracker_state_bytes(1) != RADAR_STATE_HEADER_BYTES + RADAR_TRACK_BYTES * RADAR_MAX_TRACKS:
+        raise MeError(f"radar capacities / state layout mismatch: library {got}, binding {radar}")
     _lib = lib_
     return _lib
 
@@ -848,6 +876,44 @@ def nms_indices(boxes, scores, idxs, iou_threshold):
     return keep[: int(cnt.item())].to(src)
 
 
+def nms_indices_grouped(boxes, scores, labels, group_sizes, iou_threshold):
+    """:func:`nms_indices` for several independent groups of rows with one read-back: ``boxes`` [m,4], ``scores`` [m], ``labels``
+    [m] are contiguous float32 CUDA tensors whose rows lie group after group (``group_sizes[g]`` rows each).  One
+    ``me_nms_boxes_f32`` call per non-empty group is queued on the current stream - the same call :func:`nms_indices` makes on
+    that group's rows alone - and the kept indices come back in one copy.  Returns one int64 CPU tensor per group: the kept
+    rows in descending-score order, as indices into ``boxes``."""
+    for t, name in ((boxes, "boxes"), (scores, "scores"), (labels, "labels")):
+        _require_cuda_f32(t, name)
+        if not t.is_contiguous():
+            raise MeError(f"nms_indices_grouped: {name} must be contiguous")
+    m, n = int(boxes.shape[0]), len(group_sizes)
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or scores.numel() != m or labels.numel() != m or sum(group_sizes) != m \
+            or min(group_sizes, default=0) < 0:
+        raise MeError("nms_indices_grouped: boxes [m,4], scores [m], labels [m] and group sizes that add up to m")
+    if m == 0:
+        return [torch.empty((0,), dtype=torch.int64) for _ in range(n)]
+    dev = boxes.device
+    with torch.cuda.device(dev):
+        out = torch.zeros((m + n,), dtype=torch.int64, device=dev)   # kept indices of every group, then the counts
+        cnt = torch.zeros((n,), dtype=torch.int32, device=dev)
+        ws_ptr, _keep = _workspace(lib().me_nms_workspace_bytes(1, max(group_sizes)), dev)
+        stream, start = stream_ptr(), 0
+        for g, size in enumerate(group_sizes):
+            if size:
+                rows = slice(start, start + size)
+                check(lib().me_nms_boxes_f32(boxes[rows].data_ptr(), scores[rows].data_ptr(), labels[rows].data_ptr(), size,
+                                             float(iou_threshold), out[rows].data_ptr(), cnt[g:].data_ptr(), ws_ptr, stream),
+                      "me_nms_boxes_f32")
+            start += size
+        out[m:] = cnt
+        host = out.cpu()
+    kept, start = [], 0
+    for g, size in enumerate(group_sizes):
+        kept.append(host[start:start + int(host[m + g])] + start)
+        start += size
+    return kept
+
+
 def _roi(fn_name, map_nhwc, rois, pooled, spatial_scale, ps):
     _require_cuda_f32(map_nhwc, "map")
     n, h, w, c = map_nhwc.shape
@@ -906,3 +972,17 @@ def conv_wgrad(x_nhwc, dy_nhwc, ksize, stride, pad, oihw=False):
     check(fn(x_nhwc.data_ptr(), x_nhwc.stride(2), dy_nhwc.data_ptr(), dy_nhwc.stride(2), dw.data_ptr(), n, h, w, cin, cout,
              ksize, stride, pad, ws_ptr, need, stream_ptr()), "me_conv_wgrad_mfma_f32")
     return dw
+
+
+def frame_means(imgs):
+    """One mean per frame of a contiguous float32 CUDA batch ``[n, ...]`` (``me_frame_means_f32``) -> float32 ``[n]`` on the
+    device: the ``img.mean()`` of the demos' auto mode for every frame of a batch in one launch."""
+    _require_cuda_f32(imgs, "imgs")
+    if not imgs.is_contiguous():
+        raise MeError("imgs must be contiguous")
+    n = int(imgs.shape[0])
+    means = torch.empty((n,), device=imgs.device, dtype=torch.float32)
+    if n:
+        check(lib().me_frame_means_f32(imgs.data_ptr(), n, imgs.numel() // n, means.data_ptr(), stream_ptr()),
+              "me_frame_means_f32")
+    return means

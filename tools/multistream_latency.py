@@ -1,0 +1,115 @@
+"""Latency of the multi-stream step (millieye_amd.demo.MultiStreamFuser) against S sequential FrameFuser calls on the same
+inputs: python tools/multistream_latency.py [--steps 100] [--out profiles/multistream_latency.txt]  (GPU box)
+
+Per (network, dtype, S): ms per step and frames/s of both paths (median of the repeats, warm-up first, device synchronised
+around every timed region), the radar upload + the two proposal launches (HIP events around ``DeviceRadarProposals.launch``: the
+host-side packing of the points and the copy are inside, so it bounds the launches' device time from above), one host
+generator call for one stream, and the host time of a step before its first network launch.  The "dark" rows feed 480x640
+frames that all select fusion (one ``Network.forward``, no gather); the "mixed" rows feed the tests' frames - two sizes, dark
+and bright interleaved - so that every step takes the mode split: two forwards on gathered sub-batches.  The radar streams and
+the float64 bar quoted in the first lines are those of tests/test_gpu_multistream.py (tests/multistream_helpers.py)."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from millieye_amd import cfgs, synth  # noqa: E402
+from millieye_amd.demo import FrameFuser, MultiStreamFuser  # noqa: E402
+from millieye_amd.my_models import Network  # noqa: E402
+from millieye_amd.yolov3.models import Darknet  # noqa: E402
+from tests import multistream_helpers as mh  # noqa: E402
+from tests.golden.make_golden import RADAR_CALIB, radar_points  # noqa: E402
+
+
+REPEATS = 3
+
+
+def timed(fn, steps, repeats=REPEATS):
+    out = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for f in range(steps):
+            fn(f)
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) / steps)
+    return statistics.median(out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--streams", type=int, nargs="*", default=[1, 8, 32])
+    ap.add_argument("--cfgs", nargs="*", default=["yolov3-tiny-12", "yolov3"])
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    say(f"# python tools/multistream_latency.py {' '.join(sys.argv[1:])}".rstrip())
+    say(f"# {torch.cuda.get_device_name(0)}; {args.steps} steps per repeat, median of {REPEATS} repeats, 5 warm-up steps")
+    dev = mh.kalman_deviation()
+    say(f"# float64 bar of tests/test_gpu_multistream.py: host tracker inv vs solve deviation {dev:.3e}, bar (16 x) {16 * dev:.3e}")
+    for cfg in args.cfgs:
+        for dtype in ("f32", "bf16"):
+            net = Network(Darknet(cfgs.write_cfg(cfg, f"/tmp/ms_lat_{cfg}")), 0.2).eval()
+            synth.fill_network_(net, "demo/" + cfg, cls0_bias=3.0, cls_bias=-4.0)
+            net = net.to(net.device)
+            net.base_detector.compute_dtype = dtype
+            for n, mixed in [(n, False) for n in args.streams] + [(max(args.streams), True)]:
+                if mixed:   # two frame sizes, dark and bright interleaved: both sub-batches every step
+                    frames = [mh.stream_frame(s) for s in range(n)]
+                else:       # dark: every frame selects fusion
+                    frames = [(synth.uniform(f"ms/frame{s}", (480, 640, 3)) * 25).astype(np.uint8) for s in range(n)]
+                # the seeds wrap every 45 steps: the synthetic reflectors drift out of the filter's depth range after that, and
+                # seed 46 holds a point on the camera plane (tests/multistream_helpers.py)
+                radar = [[[radar_points((f + 7 * s) % 45)] for s in range(n)] for f in range(args.steps)]
+                multi = MultiStreamFuser(net, RADAR_CALIB, n, model_mode=3, min_hits=2)
+                singles = [FrameFuser(net, RADAR_CALIB, model_mode=3, min_hits=2) for _ in range(n)]
+                for f in range(5):   # warm-up: plans, autotuner, allocator
+                    multi(frames, radar[f])
+                    for s in range(n):
+                        singles[s](frames[s], radar[f][s])
+                t_multi = timed(lambda f: multi(frames, radar[f]), args.steps)
+                t_seq = timed(lambda f: [singles[s](frames[s], radar[f][s]) for s in range(n)], args.steps)
+                # radar upload + chain + pack, HIP events (the host packs the points between the two records)
+                gen = multi.generator
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ev = []
+                for f in range(args.steps):
+                    torch.cuda.synchronize()
+                    a.record()
+                    gen.launch(radar[f])
+                    b.record()
+                    torch.cuda.synchronize()
+                    ev.append(a.elapsed_time(b))
+                t_launch = statistics.median(ev)
+                t_host_gen = timed(lambda f: singles[0].generator(radar[f][0]), args.steps)
+                # host time of a step before the first network launch: prepare + radar chain + staging + maps + mode rule
+
+                def front(f):
+                    p = multi.prepare(frames, radar[f])
+                    img = p["img"].to(multi.device)
+                    gen.gen(p["radar_frames"], p["hw"])
+                    gen.heatmaps(32)
+                    multi._modes(img)
+                t_front = timed(front, args.steps)
+                say(f"{cfg:16s} {dtype:4s} S={n:2d} {'mixed' if mixed else 'dark '}: multi {t_multi * 1e3:7.2f} ms/step "
+                    f"({n / t_multi:7.1f} frames/s) | {n} x FrameFuser {t_seq * 1e3:7.2f} ms ({n / t_seq:7.1f} frames/s) | "
+                    f"ratio {t_seq / t_multi:5.2f} | radar upload + proposal launches {t_launch:6.3f} ms | host generator, 1 stream "
+                    f"{t_host_gen * 1e3:6.3f} ms | front before the network {t_front * 1e3:6.2f} ms")
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
