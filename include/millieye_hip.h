@@ -391,7 +391,9 @@ int me_gemm_f32(int32_t trans_a, int32_t trans_b, int32_t m, int32_t n, int32_t 
 int me_colsum_f32(const float* x, int64_t ld, int32_t rows, int32_t cols, float* out, void* stream);
 /* nn.BatchNorm2d in training mode over rows of x[rows, channels] (NHWC maps: rows = n*h*w):
  * batch mean / biased variance, y = act((x-mean)*rstd*gamma+beta), running stats updated in place
- * (momentum, unbiased variance) when running_mean != NULL.  workspace: me_bn_workspace_bytes(channels). */
+ * (momentum, unbiased variance) when running_mean != NULL.  workspace: me_bn_workspace_bytes(channels) bytes, 8-byte aligned
+ * (the chunk partials of sum x and sum x^2 are doubles; a channel whose |mean| exceeds 4 std takes its statistics from them, so
+ * the variance E[x^2] - mean^2 keeps float accuracy up to mean / std ~ 1e3; below that the float-rounded partials are summed as before). */
 int64_t me_bn_workspace_bytes(int32_t channels);
 int me_bn_train_fwd_f32(const float* x, int64_t ldx, int32_t rows, int32_t channels, const float* gamma,
                         const float* beta, float eps, float momentum, float* running_mean, float* running_var,
@@ -408,6 +410,7 @@ int me_bn_train_bwd_f32(const float* x, int64_t ldx, const float* dy, int64_t ld
  *   dc = dy * act'(y) * scale (scale NULL = 1), dshift[c] = sum dy*act'(y) (= d beta, or d bias when there is no BN),
  *   dgamma[c] = sum dy*act'(y) * xhat with xhat = (act^-1(y) - beta) / gamma (gamma/beta/dgamma NULL when no BN).
  *   act: linear or leaky.  workspace: me_affine_bwd_workspace_bytes(rows, channels).  Fixed-order reductions.
+ *   A gamma[c] of exactly 0 makes xhat unrecoverable from the stored output: dgamma[c] is then 0 (dc and dshift are unaffected).
  * me_upsample2_bwd_f32: dx [n,h,w,c] += 2x2 block sums of dy [n,2h,2w,c] (nearest x2, models.py:82-92).
  * me_maxpool_bwd_f32: dx += dy routed to the first maximum of each window (MaxPool2d / ZeroPad2d+MaxPool2d, :43-49).
  * me_yolo_loss_bwd_f32: d(loss)/d(raw map) of one YOLOLayer (:196-214) from the build_targets tensors
@@ -563,7 +566,8 @@ int me_ps_roi_align_bwd_f32(const float* grad_out, const float* rois, int32_t k,
  * graph is fixed; these forms take the buffers' CAPACITY as the launch size and the live row count from a device word: rows behind it
  * produce zeros (so the dense gradient products over the whole capacity add exact zeros) and cost nothing in the scatter kernels.
  *   me_heads_tail_bwd_dev_f32     me_heads_tail_bwd_f32 over `cap` rows, zeros behind *k_dev
- *   me_bn_train_bwd_dev_f32       me_bn_train_bwd_f32 with the statistics' row count = min(*rows_dev, rows_cap), dx = 0 behind it
+ *   me_bn_train_bwd_dev_f32       me_bn_train_bwd_f32 with the statistics' row count = min(*rows_dev, rows_cap), dx = 0 behind it;
+ *                                 a live count of 0 writes dx = 0 and dgamma = dbeta = 0
  *   me_[ps_]roi_align_bwd_dev_f32 the RoI scatters over min(*k_dev, k_cap) RoIs */
 int me_heads_tail_bwd_dev_f32(const me_heads_desc* d, const float* small, const float* refine, const float* mask1,
                               const float* seed_p, const float* seed_conf, int32_t cap, const int32_t* k_dev, float* g_o,

@@ -127,8 +127,11 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict
                                                          const float* __restrict__ G, long long ldg,
                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                         int act, float* p0, float* p1, const int* rows_dev = nullptr) {
+                                                         int act, double* p0, double* p1, const int* rows_dev = nullptr) {
   // forward use (G == nullptr): p0 = sum x, p1 = sum x^2 over this block's row chunk
+  // The chunk partials are stored as DOUBLES: the variance is E[x^2] - mean^2, and a partial rounded to float carries 2^-24 of
+  // sum x^2, i.e. a relative error of the variance of ~2^-24 * (1 + (mean / std)^2) - 1e-4 at mean / std = 100, percents at 1000
+  // (bn_finish_stats_kernel decides per channel whether that matters).
   // backward use: p0 = sum g, p1 = sum g * xhat with g = dy * act'(bn output)
   // rows_dev (captured steps): the live row count in device memory, `rows` is then the buffers' capacity
   // Round 6: a block = 64 channels x 4 row lanes (a wave reads 64 consecutive channels of one row; the four lanes of a channel walk
@@ -165,8 +168,12 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict
   s1s[rl][cl] = s1;
   __syncthreads();
   if (rl == 0 && c < C) {
-    p0[(long long)chunk * C + c] = (float)(((s0s[0][cl] + s0s[1][cl]) + s0s[2][cl]) + s0s[3][cl]);
-    p1[(long long)chunk * C + c] = (float)(((s1s[0][cl] + s1s[1][cl]) + s1s[2][cl]) + s1s[3][cl]);
+    const double a = ((s0s[0][cl] + s0s[1][cl]) + s0s[2][cl]) + s0s[3][cl];
+    const double b = ((s1s[0][cl] + s1s[1][cl]) + s1s[2][cl]) + s1s[3][cl];
+    // (backward: sums of gradients have no such cancellation; their partials keep the float rounding they always had, so the
+    // gradients of a step are bit-identical with the float-partial version)
+    p0[(long long)chunk * C + c] = G ? (double)(float)a : a;
+    p1[(long long)chunk * C + c] = G ? (double)(float)b : b;
   }
 }
 
@@ -181,19 +188,30 @@ __device__ __forceinline__ void wave_sum2(double& s0, double& s1) {
   }
 }
 
-__global__ __launch_bounds__(256) void bn_finish_stats_kernel(const float* p0, const float* p1, int rows, int C,
+__global__ __launch_bounds__(256) void bn_finish_stats_kernel(const double* p0, const double* p1, int rows, int C,
                                                               float eps, float momentum, float* mean, float* var,
                                                               float* rstd, float* running_mean, float* running_var) {
   static_assert(BN_CHUNKS == 64, "one lane per chunk");
   const int lane = threadIdx.x & 63;
   const int c = blockIdx.x * 4 + (threadIdx.x >> 6);   // a wave per channel
   if (c >= C) return;
+  // Two sums of the same partials: as doubles, and rounded to float first (what this kernel always summed).  The float form
+  // loses 2^-24 * E[x^2] / var of the variance; up to |mean| = 4 std (E[x^2] <= 17 var, a few 1e-7) it is kept, so the
+  // statistics - and with them every bit of a training step on ordinarily centred activations - are what they were with
+  // float partials; beyond that the double sums take over (the float form is off by 1e-6 at mean / std 10, 1e-4 at 100).
   double s0 = p0[(long long)lane * C + c], s1 = p1[(long long)lane * C + c];
+  double f0 = (double)(float)s0, f1 = (double)(float)s1;
   wave_sum2(s0, s1);
+  wave_sum2(f0, f1);
   if (lane != 0) return;
-  const double mu = s0 / rows;
+  double mu = s0 / rows;
   double v = s1 / rows - mu * mu;
   if (v < 0.0) v = 0.0;
+  if (mu * mu <= 16.0 * v) {
+    mu = f0 / rows;
+    v = f1 / rows - mu * mu;
+    if (v < 0.0) v = 0.0;
+  }
   mean[c] = (float)mu;
   var[c] = (float)v;
   rstd[c] = (float)(1.0 / sqrt(v + (double)eps));
@@ -221,7 +239,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
                                                            const float* __restrict__ G, long long ldg, int rows,
                                                            int C, const float* mean, const float* rstd,
                                                            const float* gamma, const float* beta, int act,
-                                                           const float* p0, const float* p1, float* dgamma,
+                                                           const double* p0, const double* p1, float* dgamma,
                                                            float* dbeta, float* DX, long long lddx, const int* rows_dev = nullptr) {
   // p0[c] / p1[c] hold the channel sums (bn_reduce_partials_kernel folded the chunk partials, fixed order)
   const long long total = (long long)rows * C;   // (the capacity when rows_dev is given: rows behind the live count get dx = 0)
@@ -229,32 +247,32 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
   for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
     const int c = (int)(idx % C);
     const long long r = idx / C;
+    const double s0 = p0[c], s1 = p1[c];
+    if (r == 0) {   // (before the live-row test: with a live count of 0 the sums are 0 and are still written)
+      if (dbeta) dbeta[c] = (float)s0;
+      if (dgamma) dgamma[c] = (float)s1;
+    }
     if (r >= rows) {
       if (DX) DX[r * lddx + c] = 0.f;
       continue;
     }
-    const double s0 = p0[c], s1 = p1[c];
     const float mu = mean[c], rs = rstd[c], ga = gamma[c], be = beta[c];
     const float xh = (X[r * ld + c] - mu) * rs;
     float g = G[r * ldg + c];
     if (act == ME_ACT_LEAKY) g = (xh * ga + be > 0.f) ? g : 0.1f * g;
     if (DX) DX[r * lddx + c] = ga * rs * (g - (float)(s0 / rows) - xh * (float)(s1 / rows));
-    if (r == 0) {
-      if (dbeta) dbeta[c] = (float)s0;
-      if (dgamma) dgamma[c] = (float)s1;
-    }
   }
 }
 
-__global__ __launch_bounds__(256) void bn_reduce_partials_kernel(float* p0, float* p1, int C) {
+__global__ __launch_bounds__(256) void bn_reduce_partials_kernel(double* p0, double* p1, int C) {
   const int lane = threadIdx.x & 63;
   const int c = blockIdx.x * 4 + (threadIdx.x >> 6);   // a wave per channel; rows 1.. of the partials are read before row 0 is
   if (c >= C) return;                                  // written, and only by this wave
   double s0 = p0[(long long)lane * C + c], s1 = p1[(long long)lane * C + c];
   wave_sum2(s0, s1);
   if (lane == 0) {
-    p0[c] = (float)s0;
-    p1[c] = (float)s1;
+    p0[c] = (double)(float)s0;
+    p1[c] = (double)(float)s1;
   }
 }
 
@@ -1706,7 +1724,7 @@ int me_colsum_f32(const float* x, int64_t ld, int32_t rows, int32_t cols, float*
   return me::check_launch("colsum_kernel");
 }
 
-int64_t me_bn_workspace_bytes(int32_t channels) { return (int64_t)2 * BN_CHUNKS * channels * sizeof(float); }
+int64_t me_bn_workspace_bytes(int32_t channels) { return (int64_t)2 * BN_CHUNKS * channels * sizeof(double); }
 
 int me_bn_train_fwd_f32(const float* x, int64_t ldx, int32_t rows, int32_t channels, const float* gamma,
                         const float* beta, float eps, float momentum, float* running_mean, float* running_var,
@@ -1716,8 +1734,9 @@ int me_bn_train_fwd_f32(const float* x, int64_t ldx, int32_t rows, int32_t chann
   ME_REQUIRE(x && gamma && beta && y && save_mean && save_var && save_rstd && workspace, ME_E_NULLPTR,
              "me_bn_train_fwd_f32: null pointer");
   ME_REQUIRE(rows > 0 && channels > 0, ME_E_BADARG, "me_bn_train_fwd_f32: bad dimensions");
-  float* p0 = reinterpret_cast<float*>(workspace);
-  float* p1 = p0 + (long long)BN_CHUNKS * channels;
+  ME_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, ME_E_BADARG, "bn_train: workspace must be 8-byte aligned");
+  double* p0 = reinterpret_cast<double*>(workspace);
+  double* p1 = p0 + (long long)BN_CHUNKS * channels;
   const unsigned cb = (channels + 3) / 4;   // the finishing kernels: a wave per channel
   hipLaunchKernelGGL(bn_partial_kernel, dim3((channels + 63) / 64, BN_CHUNKS), dim3(256), 0, stream, x, (long long)ldx, rows, channels,
                      (const float*)nullptr, 0ll, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
@@ -1759,8 +1778,9 @@ static int launch_bn_train_bwd(const float* x, int64_t ldx, const float* dy, int
   ME_REQUIRE(x && dy && gamma && beta && save_mean && save_rstd && workspace, ME_E_NULLPTR,
              "me_bn_train_bwd_f32: null pointer");
   ME_REQUIRE(rows > 0 && channels > 0, ME_E_BADARG, "me_bn_train_bwd_f32: bad dimensions");
-  float* p0 = reinterpret_cast<float*>(workspace);
-  float* p1 = p0 + (long long)BN_CHUNKS * channels;
+  ME_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, ME_E_BADARG, "bn_train: workspace must be 8-byte aligned");
+  double* p0 = reinterpret_cast<double*>(workspace);
+  double* p1 = p0 + (long long)BN_CHUNKS * channels;
   const unsigned cb = (channels + 3) / 4;   // the finishing kernels: a wave per channel
   hipLaunchKernelGGL(bn_partial_kernel, dim3((channels + 63) / 64, BN_CHUNKS), dim3(256), 0, stream, x, (long long)ldx, rows, channels,
                      dy, (long long)lddy, save_mean, save_rstd, gamma, beta, act, p0, p1, rows_dev);
