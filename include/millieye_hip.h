@@ -213,6 +213,35 @@ int me_nms_candidate_counts(const void* workspace, int32_t n, int32_t rows, int3
 int me_nms_boxes_f32(const float* boxes, const float* scores, const float* labels, int32_t m, float iou_thresh,
                      int64_t* keep, int32_t* keep_count, void* workspace, void* stream);
 
+/* me_nms_boxes_grouped_f32: me_nms_boxes_f32 of `groups` independent groups of rows in one call (seven launches - zero, prep,
+ *   rank, matrix, scan, select, emit - instead of seven
+ *   per group).  boxes [m,4], scores [m], labels [m] (or NULL) hold the rows group after group; group_start [groups + 1] is a
+ *   DEVICE int32 array (group g = rows group_start[g] .. group_start[g + 1] - 1; group_start[0] = 0, group_start[groups] = m);
+ *   cap: a bound of every group's size that the host promises.  Every group has its own coordinate maximum for the offset trick
+ *   (NaN for that group only when one of its coordinates is NaN), so the kept rows of group g - written in descending-score
+ *   order as indices into boxes from keep[group_start[g]], keep_count[g] of them - equal, bit for bit and in order, what
+ *   me_nms_boxes_f32 returns on that group's rows alone, shifted by group_start[g].  A group larger than cap writes nothing and
+ *   gets keep_count[g] = -1.  keep [m] int64, keep_count [groups] int32 (device).
+ *   workspace: me_nms_workspace_bytes(groups, cap).  m, cap <= 32768, groups <= 65535. */
+int me_nms_boxes_grouped_f32(const float* boxes, const float* scores, const float* labels, const int32_t* group_start,
+                             int32_t groups, int32_t m, int32_t cap, float iou_thresh, int64_t* keep, int32_t* keep_count,
+                             void* workspace, void* stream);
+
+/* me_stream_tail_f32: the output tail of a multi-stream step (demo.MultiStreamFuser) in seven launches.  rows [m,8] are the
+ *   network's rows (stream, x1, y1, x2, y2, p, cls_score, cls_pred) in the network's order.  Per stream: batched_nms of its rows
+ *   (boxes = columns 1-4, scores = column 5, labels = column 7; ties: the row that comes first in `rows`), then the kept rows in
+ *   kept order as 7 columns with the box rescaled to the stream's frame: ((v - a) / b) * c in three separately rounded float32
+ *   operations, scalars [streams,6] = (a, b, c) for x then for y = (pad // 2, current_dim - pad, original) of
+ *   utils.rescale_boxes.  Equal to me_nms_boxes_f32 + rescale_boxes on each stream's rows alone.
+ *   out (device, 16-byte aligned, me_stream_tail_out_bytes(streams, m) bytes): int32 words [status | rows of stream s [streams] |
+ *   kept rows of stream s [streams] | padding to a multiple of 4 words], then float [m,7]: the kept rows of stream s start at
+ *   output row (rows of the streams before s); the other output rows are not written.  status bit 0: a stream column is not an
+ *   exact integer in [0, streams) - such rows are left out, nothing is written out of range, the results are not to be used.
+ *   workspace: me_nms_workspace_bytes(streams, m).  m <= 32768, streams <= 65535. */
+int64_t me_stream_tail_out_bytes(int32_t streams, int32_t m);
+int me_stream_tail_f32(const float* rows, int32_t m, int32_t streams, const float* scalars, float iou_thresh, void* out,
+                       void* workspace, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * me_gather_class_boxes_f32 - proposal assembly.
  * replaces: the per-image python loop of Network.forward, my_models.py:459-473: keep detections

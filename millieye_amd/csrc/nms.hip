@@ -1125,6 +1125,152 @@ inline int launch_matrix_path(const NmsWs& w, int n, int use_offsets, float iou_
   return me::check_launch("nms_scan_kernel");
 }
 
+
+// ---- grouped boxes / the multi-stream tail -----------------------------------------------------------------------------------
+// me_nms_boxes_grouped_f32: G independent batched_nms problems in the [n][cap] lists the kernels above already take - group g is
+// "image" g, with its own count, its own coordinate maximum and NaN flag, so every group sees exactly what me_nms_boxes_f32
+// computes on its rows alone (the joint call with the label group * classes + class would share ONE maximum).
+//
+// group of row r: the g with group_start[g] <= r < group_start[g + 1] (empty groups share a start and own no row)
+__device__ __forceinline__ int group_of_row(const int* __restrict__ group_start, int groups, int r) {
+  int lo = 0, hi = groups + 1;  // first index whose start is > r
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (group_start[mid] > r) hi = mid; else lo = mid + 1;
+  }
+  return lo - 1;
+}
+
+// one thread per row: slot [g][r - group_start[g]], the local row in the key.  A group larger than cap (or a start array that is
+// not a partition of the rows) owns no slot: its rows are skipped, its count stays 0 and the emit kernel reports -1.
+__global__ __launch_bounds__(256) void nms_prep_grouped_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                               const float* __restrict__ labels,
+                                                               const int* __restrict__ group_start, int groups, int m, NmsWs w) {
+  const int row = blockIdx.x * 256 + threadIdx.x;
+  if (row >= m) return;
+  const int g = group_of_row(group_start, groups, row);
+  if (g < 0 || g >= groups) return;
+  const int local = row - group_start[g], size = group_start[g + 1] - group_start[g];
+  if (local < 0 || local >= size || size > w.cap) return;
+  const long long o = (long long)g * w.cap + local;
+  const float x1 = boxes[4 * row], y1 = boxes[4 * row + 1], x2 = boxes[4 * row + 2], y2 = boxes[4 * row + 3];
+  w.raw[o] = make_float4(x1, y1, x2, y2);
+  w.key[o] = make_key(scores[row], local);
+  w.label[o] = labels ? labels[row] : 0.f;
+  w.clsconf[o] = 0.f;
+  if (local == 0) w.cand_count[g] = size;
+  note_max_coord(w, g, x1, y1, x2, y2);
+}
+
+__global__ __launch_bounds__(256) void nms_emit_grouped_kernel(NmsWs w, const int* __restrict__ group_start, int groups, int m,
+                                                               int* __restrict__ count, long long* __restrict__ keep) {
+  const int row = blockIdx.x * 256 + threadIdx.x;
+  if (row >= m) return;
+  const int g = group_of_row(group_start, groups, row);
+  if (g < 0 || g >= groups) return;
+  const int start = group_start[g], local = row - start, size = group_start[g + 1] - start;
+  if (local < 0 || local >= size) return;
+  if (size > w.cap) {  // (the selection kernels wrote 0 for the empty list)
+    if (local == 0) count[g] = -1;
+    return;
+  }
+  if (local >= count[g]) return;
+  const long long base = (long long)g * w.cap;
+  const unsigned long long key = w.key[base + w.keep_slot[base + local]];
+  keep[row] = (long long)start + (long long)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
+}
+
+// me_stream_tail_f32.  Output buffer: int32 header [status | rows per stream [S] | kept rows per stream [S] | padding to a
+// multiple of 4 words], then float rows [m][7]; stream s owns the output rows from the sum of the earlier streams' row counts.
+__host__ __device__ inline int tail_head_words(int streams) { return (1 + 2 * streams + 3) & ~3; }
+
+__global__ __launch_bounds__(256) void tail_zero_kernel(int* ws_ints, int ws_count, int* head, int head_count) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < ws_count) ws_ints[i] = 0;
+  if (i < head_count) head[i] = 0;
+}
+
+// one thread per network row: the stream column picks the list; the slot comes from one atomic per (wave, stream) - the order of
+// the slots does not matter, the key carries the row, and among one stream's rows the lower row is the earlier one in the
+// network's order: the tie rule of the stable grouping torch.sort(rows[:, 0], stable=True) + batched_nms.
+__global__ __launch_bounds__(256) void tail_prep_kernel(const float* __restrict__ rows, int m, int streams, NmsWs w,
+                                                        int* __restrict__ status) {
+  const int row = blockIdx.x * 256 + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  int s = -1;
+  if (row < m) {
+    const float sv = rows[8ll * row];
+    if (sv >= 0.f && sv < (float)streams && sv == floorf(sv)) s = (int)sv;
+    else atomicOr(status, 1);
+  }
+  int slot = -1;
+  unsigned long long todo = __builtin_amdgcn_ballot_w64(s >= 0);
+  while (todo != 0ull) {
+    const int leader = __builtin_ctzll(todo);
+    const int ls = __builtin_amdgcn_readlane(s, leader);
+    const unsigned long long same = __builtin_amdgcn_ballot_w64(s == ls);
+    int base = 0;
+    if (lane == leader) base = atomicAdd(&w.cand_count[ls], __builtin_popcountll(same));
+    base = __builtin_amdgcn_readlane(base, leader);
+    if (s == ls) slot = base + __builtin_popcountll(same & ((1ull << lane) - 1ull));
+    todo &= ~same;
+  }
+  if (s < 0 || slot < 0 || slot >= w.cap) return;  // (cap = m: a slot past it cannot happen)
+  const float* p = rows + 8ll * row;
+  const long long o = (long long)s * w.cap + slot;
+  w.raw[o] = make_float4(p[1], p[2], p[3], p[4]);
+  w.key[o] = make_key(p[5], row);
+  w.label[o] = p[7];
+  w.clsconf[o] = p[6];
+  note_max_coord(w, s, p[1], p[2], p[3], p[4]);
+}
+
+// one thread per output row j: stream s with start_s <= j < start_s + rows_s, k = j - start_s; the k-th kept row of the stream
+// with the box rescaled to the stream's frame: ((v - pad // 2) / unpadded) * original, three separately rounded operations
+// (utils.rescale_boxes; scal[s] = x: pad // 2, unpadded, original; y: the same)
+__global__ __launch_bounds__(256) void tail_emit_kernel(const float* __restrict__ rows, int m, int streams, NmsWs w,
+                                                        const float* __restrict__ scal, int* __restrict__ head,
+                                                        float* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  const int* kept = head + 1 + streams;
+  if (j < streams) head[1 + j] = w.cand_count[j];
+  if (j >= m) return;
+  int s = 0, start = 0;
+  for (; s < streams; ++s) {
+    const int c = w.cand_count[s];
+    if (j < start + c) break;
+    start += c;
+  }
+  if (s >= streams) return;  // (rows with a bad stream column were not listed)
+  const int k = j - start;
+  if (k >= kept[s]) return;
+  const long long base = (long long)s * w.cap;
+  const unsigned long long key = w.key[base + w.keep_slot[base + k]];
+  const int row = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
+  if (row < 0 || row >= m) return;
+  const float* p = rows + 8ll * row;
+  const float* c = scal + 6 * s;
+  float* o = out + 7ll * j;
+  o[0] = __fmul_rn(__fdiv_rn(__fsub_rn(p[1], c[0]), c[1]), c[2]);
+  o[1] = __fmul_rn(__fdiv_rn(__fsub_rn(p[2], c[3]), c[4]), c[5]);
+  o[2] = __fmul_rn(__fdiv_rn(__fsub_rn(p[3], c[0]), c[1]), c[2]);
+  o[3] = __fmul_rn(__fdiv_rn(__fsub_rn(p[4], c[3]), c[4]), c[5]);
+  o[4] = p[5];
+  o[5] = p[6];
+  o[6] = p[7];
+}
+
+// rank / matrix / scan + the single-workgroup kernel for the lists it leaves: the selection of n lists, every winner kept
+inline int select_all(const NmsWs& w, int n, int use_offsets, float iou_thresh, int* out_count, hipStream_t stream) {
+  int rc = launch_matrix_path(w, n, use_offsets, iou_thresh, w.cap, out_count, stream);
+  if (rc) return rc;
+  ME_HIP(select_lds_attr());
+  hipLaunchKernelGGL(nms_select_kernel, dim3(n), dim3(SEL_THREADS), kSelectLds, stream, w, use_offsets, iou_thresh, w.cap,
+                     out_count);
+  return me::check_launch("nms_select_kernel");
+}
+
 }  // namespace
 
 extern "C" {
@@ -1266,6 +1412,68 @@ int me_nms_boxes_f32(const float* boxes, const float* scores, const float* label
   hipLaunchKernelGGL(nms_emit_indices_kernel, dim3((m + 255) / 256), dim3(256), 0, stream, w, keep_count,
                      reinterpret_cast<long long*>(keep));
   return me::check_launch("nms_emit_indices_kernel");
+}
+
+int me_nms_boxes_grouped_f32(const float* boxes, const float* scores, const float* labels, const int32_t* group_start,
+                             int32_t groups, int32_t m, int32_t cap, float iou_thresh, int64_t* keep, int32_t* keep_count,
+                             void* workspace, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  ME_REQUIRE(keep_count && group_start, ME_E_NULLPTR, "me_nms_boxes_grouped_f32: null keep_count / group_start");
+  ME_REQUIRE(groups > 0 && groups <= 65535 && m >= 0, ME_E_BADARG, "me_nms_boxes_grouped_f32: bad groups / m");
+  if (m == 0) {
+    hipLaunchKernelGGL(zero_ints_kernel, dim3((groups + 255) / 256), dim3(256), 0, stream, keep_count, groups);
+    return me::check_launch("zero_ints_kernel");
+  }
+  ME_REQUIRE(boxes && scores && keep && workspace, ME_E_NULLPTR, "me_nms_boxes_grouped_f32: null pointer");
+  ME_REQUIRE(m <= MAX_ROWS && cap > 0 && cap <= MAX_ROWS, ME_E_TOOBIG, "me_nms_boxes_grouped_f32: m %d / cap %d outside (0, %d]",
+             m, cap, MAX_ROWS);
+  ME_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, ME_E_ALIGN,
+             "me_nms_boxes_grouped_f32: workspace not 256-byte aligned");
+  NmsWs w = carve(workspace, groups, cap);
+  hipLaunchKernelGGL(zero_ints_kernel, dim3((4 * groups + 255) / 256), dim3(256), 0, stream, w.cand_count, 4 * groups);
+  hipLaunchKernelGGL(nms_prep_grouped_kernel, dim3((m + 255) / 256), dim3(256), 0, stream, boxes, scores, labels, group_start,
+                     groups, m, w);
+  int rc = me::check_launch("nms_prep_grouped_kernel");
+  if (rc) return rc;
+  rc = select_all(w, groups, labels ? 1 : 0, iou_thresh, keep_count, stream);
+  if (rc) return rc;
+  hipLaunchKernelGGL(nms_emit_grouped_kernel, dim3((m + 255) / 256), dim3(256), 0, stream, w, group_start, groups, m, keep_count,
+                     reinterpret_cast<long long*>(keep));
+  return me::check_launch("nms_emit_grouped_kernel");
+}
+
+int64_t me_stream_tail_out_bytes(int32_t streams, int32_t m) {
+  if (streams <= 0 || m < 0) return 0;
+  return 4ll * tail_head_words(streams) + 28ll * m;
+}
+
+int me_stream_tail_f32(const float* rows, int32_t m, int32_t streams, const float* scalars, float iou_thresh, void* out,
+                       void* workspace, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  ME_REQUIRE(out, ME_E_NULLPTR, "me_stream_tail_f32: null output");
+  ME_REQUIRE(streams > 0 && streams <= 65535 && m >= 0, ME_E_BADARG, "me_stream_tail_f32: bad streams / m");
+  ME_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15u) == 0, ME_E_ALIGN, "me_stream_tail_f32: output not 16-byte aligned");
+  int* head = reinterpret_cast<int*>(out);
+  const int hw = tail_head_words(streams);
+  if (m == 0) {
+    hipLaunchKernelGGL(zero_ints_kernel, dim3((hw + 255) / 256), dim3(256), 0, stream, head, hw);
+    return me::check_launch("zero_ints_kernel");
+  }
+  ME_REQUIRE(rows && scalars && workspace, ME_E_NULLPTR, "me_stream_tail_f32: null pointer");
+  ME_REQUIRE(m <= MAX_ROWS, ME_E_TOOBIG, "me_stream_tail_f32: m %d > capacity %d", m, MAX_ROWS);
+  ME_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, ME_E_ALIGN, "me_stream_tail_f32: workspace not 256-byte aligned");
+  NmsWs w = carve(workspace, streams, m);  // cap = m: a bound of every stream's rows the host holds without a read-back
+  const int zc = 4 * streams > hw ? 4 * streams : hw;
+  hipLaunchKernelGGL(tail_zero_kernel, dim3((zc + 255) / 256), dim3(256), 0, stream, w.cand_count, 4 * streams, head, hw);
+  hipLaunchKernelGGL(tail_prep_kernel, dim3((m + 255) / 256), dim3(256), 0, stream, rows, m, streams, w, head);
+  int rc = me::check_launch("tail_prep_kernel");
+  if (rc) return rc;
+  rc = select_all(w, streams, 1, iou_thresh, head + 1 + streams, stream);
+  if (rc) return rc;
+  const int ec = m > streams ? m : streams;
+  hipLaunchKernelGGL(tail_emit_kernel, dim3((ec + 255) / 256), dim3(256), 0, stream, rows, m, streams, w, scalars, head,
+                     reinterpret_cast<float*>(head + hw));
+  return me::check_launch("tail_emit_kernel");
 }
 
 }  // extern "C"

@@ -13,7 +13,9 @@ serial-port capture, OpenCV window).  ``millieye_amd/pi
 
 :class:`MultiStreamFuser` is the same step for S camera + radar nodes behind one card: the radar chain of every stream on the
 device (``radar_proposals.DeviceRadarProposals``), one ragged-batch launch for the frames, one heat-map launch from the device
-cloud, per-frame means for the mode rule and at most two ``Network.forward`` calls (the fusion frames, the camera-only frames).
+cloud, per-frame means for the mode rule, at most two ``Network.forward`` calls (the fusion frames, the camera-only frames) and
+one pass over the network's rows for the output tail (``me_stream_tail_f32``: the second NMS of every stream and the rescale to
+its frame, one copy back).  ``pipeline.FusionPipeline`` runs its host half (:func:`prepare_streams`) in the producer process.
 
 Parity: every numeric stage is one of the pinned pieces (input kernels: tests/golden/dataset_small; Network.forward:
 network_*.npz; NMS: nms_synth; radar proposals: radar_proposals_synth + the unpinned Kalman part); the glue in this file
@@ -25,9 +27,9 @@ import torch
 from . import hip
 from .radar_proposals import DeviceRadarProposals, RadarProposalGenerator
 from .utils.datasets import StagedImages, StagedRadarMaps, StagedRaggedImages, _pad_amounts
-from .utils.utils import box_ops, rescale_boxes
+from .utils.utils import box_ops, rescale_boxes, rescale_scalars
 
-__all__ = ["mode_selection", "radar_boxes_for_network", "FrameFuser", "MultiStreamFuser"]
+__all__ = ["mode_selection", "radar_boxes_for_network", "prepare_streams", "FrameFuser", "MultiStreamFuser"]
 
 
 def mode_selection(mode, img, dark_threshold=0.08):
@@ -103,6 +105,24 @@ class FrameFuser:
                           points=payload["points"])
 
 
+def prepare_streams(frames, radar_frames, streams, img_size=416, pack=False):
+    """Host half of a :class:`MultiStreamFuser` step: checks and stages the raw frame bytes and radar frames (picklable; the
+    trackers live on the device, so the radar chain itself belongs to ``infer``).  Needs neither a model nor the HIP library:
+    ``pipeline.FusionPipeline`` calls it in the producer process with ``pack=True``, which also does the host loop of
+    ``StagedRaggedImages.to`` - every frame's bytes into one buffer + the descriptor - so the consumer only uploads."""
+    if len(frames) != streams or len(radar_frames) != streams:
+        raise hip.MeError(f"MultiStreamFuser: {len(frames)} frames / {len(radar_frames)} radar lists for {streams} streams")
+    frames = [torch.as_tensor(f) for f in frames]
+    for i, frame in enumerate(frames):
+        if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3:
+            raise hip.MeError(f"stream {i}: frame must be uint8 [h,w,3] (got {frame.dtype} {tuple(frame.shape)})")
+    img = StagedRaggedImages(frames, img_size)
+    if pack:
+        img.pack(keep_frames=False)
+    return dict(hw=[(int(f.shape[0]), int(f.shape[1])) for f in frames], img=img,
+                radar_frames=[list(r) for r in radar_frames])
+
+
 class MultiStreamFuser:
     """:class:`FrameFuser` for ``streams`` camera + radar nodes in one step: ``fuser(frames, radar_frames)`` takes S uint8
     ``[h,w,3]`` frames (sizes may differ per stream) and S lists of radar frames and returns a list of S ``(rows [m,7], info)``
@@ -111,33 +131,67 @@ class MultiStreamFuser:
 
     Per step: one upload + two launches for the radar chain, one ragged-batch launch for the frames, one heat-map launch, one
     launch for the per-frame means (auto mode), ``Network.forward`` once for the frames that select fusion and once for the
-    camera-only ones, the second NMS of every stream queued back to back, ``rescale_boxes`` per stream on the host rows.
+    camera-only ones, then the output tail.
 
-    The second NMS is one ``me_nms_boxes_f32`` call per stream, not one call with the label ``stream * num_classes + class``:
-    that entry point separates labels with torchvision's offset trick (``boxes + label * (max + 1)`` in float32), not by
-    equality, so a joint call would round the boxes of the later streams differently from the per-frame call of the demos."""
+    ``tail="device"`` (default): ``hip.stream_tail`` - the network's rows are listed per stream on the device, one segmented
+    NMS handles every stream (seven launches in all), the kept rows come back rescaled to each stream's frame in one copy.
+    ``tail="host"``: the rows are sorted by stream with torch and copied, one ``me_nms_boxes_f32`` call per stream is queued
+    (the same seven launches each) and ``rescale_boxes`` runs per stream on the host rows.  Both give ``torch.equal`` rows;
+    on an MI355X the tail alone takes 0.05 - 0.17 ms on the device against 0.15 - 2.5 ms on the host (S = 1 .. 32) and the whole
+    step is 10 - 42 % shorter in every row of ``profiles/multistream_latency.txt``.
+
+    The device tail lists every stream in a ``[streams][m]`` workspace (``m`` = the rows of the step, the one bound of a
+    stream's rows the host holds without a read-back): it raises :class:`hip.MeError` for more than 32768 rows in a step, where
+    the host tail only needs every stream's own rows to stay under that, and its workspace grows as ``streams * m``.
+
+    A joint ``me_nms_boxes_f32`` call with the label ``stream * num_classes + class`` would NOT: that entry point separates
+    labels with torchvision's offset trick (``boxes + label * (max + 1)`` in float32), not by equality, so one maximum shared
+    by all streams rounds the boxes of the later streams differently from the per-frame call of the demos.  The segmented call
+    keeps one maximum per stream - the NMS kernels are batched over lists that each have their own - and so reproduces the
+    per-stream calls bit for bit.
+
+    The device generator (``DeviceRadarProposals``) is built on first use of :attr:`generator` - by the first :meth:`infer` or
+    :meth:`advance` - not by the constructor: the host half (:meth:`prepare`, :func:`prepare_streams`) and
+    ``pipeline.FusionPipeline``'s consumer set-up need no GPU.  Bad calibration or generator arguments and a missing GPU therefore
+    raise at that first use; touch ``fuser.generator`` after construction to have them raise early."""
 
     def __init__(self, model, calib_params, streams, model_mode=3, img_size=416, nms_iou=0.3, dark_threshold=0.08,
-                 **generator_kwargs):
+                 tail="device", **generator_kwargs):
         self.model, self.model_mode, self.img_size, self.streams = model, model_mode, img_size, int(streams)
         self.nms_iou, self.dark_threshold = nms_iou, dark_threshold
-        self.device = getattr(model, "device", None) or hip.default_device()
-        self.generator = DeviceRadarProposals(calib_params, streams, device=self.device, **generator_kwargs)
+        if tail not in ("device", "host"):
+            raise hip.MeError(f"MultiStreamFuser: tail must be 'device' or 'host' (got {tail!r})")
+        if self.streams <= 0:
+            raise hip.MeError(f"MultiStreamFuser: streams must be positive (got {streams})")
+        self.tail = tail
+        self.calib_params, self.generator_kwargs = calib_params, generator_kwargs
+        self._device = getattr(model, "device", None)
+        self._generator = None
+        self._scalars = (None, None)   # (frame sizes, their rescale scalars on the device)
+
+    @property
+    def device(self):
+        if self._device is None:
+            self._device = hip.default_device()
+        return self._device
+
+    @property
+    def generator(self):
+        if self._generator is None:
+            self._generator = DeviceRadarProposals(self.calib_params, self.streams, device=self.device, **self.generator_kwargs)
+        return self._generator
 
     def __call__(self, frames, radar_frames):
         return self.infer(self.prepare(frames, radar_frames))
 
-    def prepare(self, frames, radar_frames):
-        """Host half: checks and stages the raw frame bytes and radar frames (picklable; the trackers live on the device, so
-        the radar chain itself belongs to :meth:`infer`)."""
-        if len(frames) != self.streams or len(radar_frames) != self.streams:
-            raise hip.MeError(f"MultiStreamFuser: {len(frames)} frames / {len(radar_frames)} radar lists for {self.streams} streams")
-        frames = [torch.as_tensor(f) for f in frames]
-        for i, frame in enumerate(frames):
-            if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3:
-                raise hip.MeError(f"stream {i}: frame must be uint8 [h,w,3] (got {frame.dtype} {tuple(frame.shape)})")
-        return dict(hw=[(int(f.shape[0]), int(f.shape[1])) for f in frames], img=StagedRaggedImages(frames, self.img_size),
-                    radar_frames=[list(r) for r in radar_frames])
+    def prepare(self, frames, radar_frames, pack=False):
+        """Host half (:func:`prepare_streams`): a picklable payload for :meth:`infer` / :meth:`advance`."""
+        return prepare_streams(frames, radar_frames, self.streams, self.img_size, pack=pack)
+
+    def advance(self, payload):
+        """The radar chain of one step and nothing else - what :meth:`infer` does first: a step whose detections nobody
+        will look at (``FusionPipeline`` skipping to the newest frames) still reaches the trackers."""
+        return self.generator.gen(payload["radar_frames"], payload["hw"])
 
     def _modes(self, img):
         if self.model_mode != 3:
@@ -172,16 +226,28 @@ class MultiStreamFuser:
                     rows = torch.cat([where[rows[:, 0].long()].to(rows.dtype)[:, None], rows[:, 1:]], 1)
                 outs.append(rows)
             rows = torch.cat(outs, 0) if len(outs) > 1 else outs[0]
-            per_stream = self._second_nms(rows)
+            per_stream = self._tail(rows, hws)
         proposals = self.generator._proposals.cpu().numpy()
         result = []
         for s in range(n):
             r = per_stream[s]
-            if len(r):
-                rescale_boxes(r, self.img_size, hws[s])
             result.append((r, dict(mode=modes[s], proposals=proposals[s, :int(counts[s, 7])].copy(),
                                    radar_boxes=int(counts[s, 4]), points=int(counts[s, 1]))))
         return result
+
+    def _tail(self, rows, hws):
+        """Network rows ``[m,8]`` (stream in column 0) -> per stream the ``[k,7]`` CPU rows after the second NMS, in pixels of
+        the stream's frame."""
+        if self.tail == "device":
+            key = tuple(hws)
+            if self._scalars[0] != key:   # the frame sizes rarely change: their scalars stay on the device
+                self._scalars = (key, rescale_scalars(self.img_size, hws).to(rows.device))
+            return hip.stream_tail(rows.to(torch.float32).contiguous(), self.streams, self._scalars[1], self.nms_iou)[0]
+        per_stream = self._second_nms(rows)
+        for s, r in enumerate(per_stream):
+            if len(r):
+                rescale_boxes(r, self.img_size, hws[s])
+        return per_stream
 
     def _second_nms(self, rows):
         """``box_ops.batched_nms(rows[:, :4], rows[:, 4], rows[:, 6], nms_iou)`` of every stream's rows (stream = column 0 of

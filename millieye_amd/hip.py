@@ -231,6 +231,11 @@ SIGNATURES = {
     "me_nms_batched_f32": (C.c_int, [C.POINTER(NmsDesc), C.c_void_p]),
     "me_nms_boxes_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "me_nms_boxes_grouped_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "me_stream_tail_out_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "me_stream_tail_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
     "me_gather_class_boxes_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "me_roi_heads_f32": (C.c_int, [C.POINTER(HeadsDesc), C.c_void_p]),
@@ -912,6 +917,80 @@ def nms_indices_grouped(boxes, scores, labels, group_sizes, iou_threshold):
         kept.append(host[start:start + int(host[m + g])] + start)
         start += size
     return kept
+
+
+def nms_indices_segmented(boxes, scores, labels, group_sizes, iou_threshold, cap=None):
+    """:func:`nms_indices_grouped` in ONE ``me_nms_boxes_grouped_f32`` call (seven launches for all groups - zero, prep, rank,
+    matrix, scan, select, emit - instead of seven per group; every group keeps its own coordinate maximum, so the kept indices are those of the per-group calls, bit for bit and
+    in order).  ``labels`` may be ``None`` (plain ``nms`` per group).  ``cap``: the bound of the group sizes given to the
+    library (default: the largest group); a group over it raises :class:`MeError` naming the group."""
+    for t, name in ((boxes, "boxes"), (scores, "scores")) + (((labels, "labels"),) if labels is not None else ()):
+        _require_cuda_f32(t, name)
+        if not t.is_contiguous():
+            raise MeError(f"nms_indices_segmented: {name} must be contiguous")
+    m, n = int(boxes.shape[0]), len(group_sizes)
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or scores.numel() != m or (labels is not None and labels.numel() != m) \
+            or n == 0 or sum(group_sizes) != m or min(group_sizes) < 0:
+        raise MeError("nms_indices_segmented: boxes [m,4], scores [m], labels [m] and group sizes that add up to m")
+    if m == 0:
+        return [torch.empty((0,), dtype=torch.int64) for _ in range(n)]
+    cap = max(group_sizes) if cap is None else int(cap)
+    if cap <= 0:
+        raise MeError(f"nms_indices_segmented: cap must be positive (got {cap})")
+    dev = boxes.device
+    starts = [0]
+    for size in group_sizes:
+        starts.append(starts[-1] + int(size))
+    with torch.cuda.device(dev):
+        d_start = torch.tensor(starts, dtype=torch.int32).to(dev)
+        out = torch.zeros((m + n,), dtype=torch.int64, device=dev)   # kept indices of every group, then the counts
+        cnt = torch.zeros((n,), dtype=torch.int32, device=dev)
+        ws_ptr, _keep = _workspace(lib().me_nms_workspace_bytes(n, cap), dev)
+        check(lib().me_nms_boxes_grouped_f32(boxes.data_ptr(), scores.data_ptr(), labels.data_ptr() if labels is not None else None,
+                                             d_start.data_ptr(), n, m, cap, float(iou_threshold), out.data_ptr(), cnt.data_ptr(),
+                                             ws_ptr, stream_ptr()), "me_nms_boxes_grouped_f32")
+        out[m:] = cnt
+        host = out.cpu()
+    for g in range(n):
+        if int(host[m + g]) < 0:
+            raise MeError(f"nms_indices_segmented: group {g} holds {group_sizes[g]} rows, more than cap = {cap}")
+    return [host[starts[g]:starts[g] + int(host[m + g])].clone() for g in range(n)]
+
+
+def stream_tail(rows, streams, scalars, iou_threshold):
+    """The output tail of a multi-stream step (``me_stream_tail_f32``): ``rows`` [m,8] float32 CUDA rows of ``Network.forward``
+    (stream in column 0, any order), ``scalars`` [streams,6] float32 CUDA (``utils.utils.rescale_scalars``).  Per stream the second NMS
+    and the rescale to its frame, one device-to-host copy for everything.  Returns ``(per_stream, in_counts)``: a list of
+    ``[k,7]`` float32 CPU tensors (kept rows in kept order, boxes in frame pixels) and the rows every stream had."""
+    _require_cuda_f32(rows, "rows")
+    _require_cuda_f32(scalars, "scalars")
+    streams = int(streams)
+    if rows.dim() != 2 or rows.shape[1] != 8 or not rows.is_contiguous() or tuple(scalars.shape) != (streams, 6) \
+            or not scalars.is_contiguous() or streams <= 0:
+        raise MeError(f"stream_tail: contiguous rows [m,8] and scalars [{streams},6] (got {tuple(rows.shape)}, "
+                      f"{tuple(scalars.shape)})")
+    m, dev = int(rows.shape[0]), rows.device
+    head = (1 + 2 * streams + 3) & ~3
+    with torch.cuda.device(dev):
+        nbytes = int(lib().me_stream_tail_out_bytes(streams, m))
+        if nbytes != 4 * head + 28 * m:
+            raise MeError(f"stream_tail: output layout mismatch (library {nbytes} bytes, binding {4 * head + 28 * m})")
+        out = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        ws_ptr, _keep = _workspace(lib().me_nms_workspace_bytes(streams, max(m, 1)), dev)
+        check(lib().me_stream_tail_f32(rows.data_ptr(), m, streams, scalars.data_ptr(), float(iou_threshold), out.data_ptr(),
+                                       ws_ptr, stream_ptr()), "me_stream_tail_f32")
+        host = out.cpu()   # the one copy: status, counts and the kept rows of every stream
+    ints = host[:4 * head].view(torch.int32)
+    if int(ints[0]):
+        raise MeError(f"stream_tail: a row's stream column is not an integer in [0, {streams})")
+    in_counts = ints[1:1 + streams].tolist()
+    kept = ints[1 + streams:1 + 2 * streams].tolist()
+    table = host[4 * head:].view(torch.float32).reshape(m, 7)
+    per_stream, start = [], 0
+    for s in range(streams):
+        per_stream.append(table[start:start + kept[s]].clone())
+        start += in_counts[s]
+    return per_stream, in_counts
 
 
 def _roi(fn_name, map_nhwc, rois, pooled, spatial_scale, ps):

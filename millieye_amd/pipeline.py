@@ -10,6 +10,14 @@ reference; the device half is :meth:`millieye_amd.demo.FrameFuser.infer`, the ho
 Video decoding, the serial-port capture and the OpenCV window are not part of the path: frames come from a caller-supplied
 *source factory* - a picklable callable returning an iterator of ``(frame_uint8_hwc, radar_frames)`` - which is called
 inside the producer process (like the reference opens ``cv2.VideoCapture`` there).
+
+With a :class:`millieye_amd.demo.MultiStreamFuser` the same two processes carry S streams per step: the source yields
+``(frames, radar_frames)`` with S entries each; the producer runs the model-free host half (``demo.prepare_streams``: the
+checks and the packing of every frame's bytes into one buffer + descriptor - most of the host time of a step at S = 32) and
+never touches the HIP library or the GPU.  The trackers live on the device, in the consumer, so the producer never drops a
+step (a dropped step would lose its radar frames and break the tracks): it blocks on the full queue, and the consumer skips
+instead - it takes everything that waits, runs ``advance`` (the radar chain alone) on all but the newest step, in order, and
+``infer`` on the newest.
 """
 import multiprocessing as mp
 import pickle
@@ -54,6 +62,37 @@ def _producer(q, first_done, all_done, source_factory, prepare_factory, drop_old
         all_done.wait(timeout=120)
 
 
+def _producer_multi(q, first_done, all_done, source_factory, prepare_factory):
+    """The producer of a multi-stream pipeline: every step is queued (blocking ``put``), skipping is the consumer's business."""
+    error = None
+    try:
+        prepare = prepare_factory()
+        for idx, (frames, radar_frames) in enumerate(source_factory()):
+            payload = prepare(frames, radar_frames)
+            payload["frame_idx"] = idx
+            q.put(payload)
+            if idx == 0:
+                first_done.wait()
+    except BaseException as exc:
+        error = f"{type(exc).__name__}: {exc}\n{traceback.format_exc()}"
+    finally:
+        q.put({"frame_idx": _END, "dropped": 0, "error": error})
+        all_done.wait(timeout=120)
+
+
+class _MultiPrepareFactory:
+    """Picklable recipe of the multi-stream host half: ``demo.prepare_streams`` with the frames packed - no model, no
+    generator, no HIP library."""
+
+    def __init__(self, streams, img_size):
+        self.streams, self.img_size = int(streams), img_size
+
+    def __call__(self):
+        import functools
+        from .demo import prepare_streams
+        return functools.partial(prepare_streams, streams=self.streams, img_size=self.img_size, pack=True)
+
+
 class _PrepareFactory:
     """Picklable recipe of the host half: builds a fresh ``FrameFuser`` (without a model) in the producer."""
 
@@ -77,11 +116,24 @@ class FusionPipeline:
     ``FrameFuser(generator=...)`` is sent there by pickle as it is now, and refused (``TypeError``) when it cannot be
     pickled - never silently replaced.  ``infer``: override of the device half (tests).  ``drop_oldest=False`` turns the
     reference's newest-wins policy into back-pressure (every frame is processed).  A failure in the producer (source,
-    tracking, staging) ends the iteration with :class:`ProducerError` carrying the producer's traceback."""
+    tracking, staging) ends the iteration with :class:`ProducerError` carrying the producer's traceback.
 
-    def __init__(self, fuser, source_factory, infer=None, drop_oldest=True, prepare_factory=None, start_method="spawn"):
+    ``fuser``: a :class:`millieye_amd.demo.MultiStreamFuser` - ``for results, info in FusionPipeline(fuser, source_factory)``
+    yields per step the list of S ``(rows, info)`` its ``infer`` returns and ``info = dict(frame_idx=..., skipped=[...])``,
+    the steps that were only advanced since the previous yield.  The source yields ``(frames, radar_frames)`` with S entries
+    each.  ``skip_to_newest=True`` (default): of the steps that wait, all but the newest only run ``advance`` (the radar
+    chain, so the trackers see every step in order); ``False``: every step is inferred.  ``stats["dropped"]`` counts the
+    skipped steps.  ``drop_oldest`` does not apply: the producer never drops.  ``advance``: override (tests)."""
+
+    def __init__(self, fuser, source_factory, infer=None, drop_oldest=True, prepare_factory=None, start_method="spawn",
+                 skip_to_newest=True, advance=None):
         self.fuser, self.source_factory, self.drop_oldest = fuser, source_factory, drop_oldest
         self.infer = infer or fuser.infer
+        self.multi = hasattr(fuser, "streams") and hasattr(fuser, "advance")
+        self.skip_to_newest = skip_to_newest
+        self.advance = advance or getattr(fuser, "advance", None)
+        if prepare_factory is None and self.multi:
+            prepare_factory = _MultiPrepareFactory(fuser.streams, fuser.img_size)
         if prepare_factory is None:
             g = fuser.generator
             if getattr(fuser, "generator_is_default", False):
@@ -113,7 +165,54 @@ class FusionPipeline:
                         raise ProducerError(f"the producer process died without ending the stream (exit code "
                                             f"{proc.exitcode})") from None
 
+    def _iter_multi(self):
+        ctx = self.ctx
+        q = ctx.Queue(maxsize=QUEUE_SIZE)
+        first_done = ctx.Event()
+        all_done = ctx.Event()
+        proc = ctx.Process(target=_producer_multi, args=(q, first_done, all_done, self.source_factory, self.prepare_factory),
+                           daemon=True)
+        proc.start()
+        t0, frames, dropped = time.perf_counter(), 0, 0
+        end = None
+        try:
+            while end is None:
+                waiting = [self._next_payload(q, proc)]
+                while self.skip_to_newest and waiting[-1]["frame_idx"] != _END:   # everything else that waits, in order
+                    try:
+                        waiting.append(q.get_nowait())
+                    except _queue.Empty:
+                        break
+                if waiting[-1]["frame_idx"] == _END:
+                    end = waiting.pop()
+                skipped = []
+                for payload in waiting[:-1]:
+                    self.advance(payload)
+                    skipped.append(payload["frame_idx"])
+                dropped += len(skipped)
+                if waiting:
+                    results = self.infer(waiting[-1])
+                    first_done.set()
+                    frames += 1
+                    yield results, dict(frame_idx=waiting[-1]["frame_idx"], skipped=skipped)
+            if end.get("error"):
+                raise ProducerError("the producer process failed:\n" + end["error"])
+        finally:
+            first_done.set()
+            all_done.set()
+            if end is None:
+                proc.terminate()   # left early (break, an exception in infer): the producer may be blocked on the full queue
+            proc.join(timeout=10)
+            if proc.is_alive():
+                proc.terminate()
+            self.stats = dict(dropped=dropped, frames=frames, seconds=time.perf_counter() - t0)
+
     def __iter__(self):
+        if self.multi:
+            return self._iter_multi()
+        return self._iter_single()
+
+    def _iter_single(self):
         ctx = self.ctx
         q = ctx.Queue(maxsize=QUEUE_SIZE)
         first_done = ctx.Event()

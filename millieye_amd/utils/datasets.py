@@ -126,14 +126,13 @@ class StagedRaggedImages(StagedImages):
     ``me_image_batch_pad_resize_flip_u8_f32`` writes ``[n,3,size,size]`` (bit-identical to the per-frame kernel).  ``.type()``
     accepts the CUDA float tensor types, for callers that write ``imgs.type(torch.cuda.FloatTensor)``."""
 
-    def to(self, device, *_, **__):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise hip.MeError("StagedRaggedImages.to(): the batch is assembled by the HIP library - CUDA device required")
+    packed = desc = None   # set by pack(): the frames' bytes in one uint8 buffer and the [n,4] int64 descriptor
+
+    def pack(self, pin=False, keep_frames=True):
+        """The host half of :meth:`to`, callable ahead of time and without a GPU (``pin=False``): checks the frames and copies
+        their bytes into one buffer.  The object then carries ``packed`` / ``desc`` (through pickle too) and :meth:`to` only
+        uploads them; ``keep_frames=False`` drops the per-frame tensors so that the bytes travel once."""
         n = len(self.frames)
-        out = torch.empty(tuple(self.shape), device=device, dtype=torch.float32)
-        if n == 0:
-            return out
         desc = torch.empty((n, 4), dtype=torch.int64)
         total = 0
         for i, frame in enumerate(self.frames):
@@ -142,10 +141,29 @@ class StagedRaggedImages(StagedImages):
                 raise hip.MeError(f"frame {i}: expected uint8 [h,w,3], got {frame.dtype} {tuple(frame.shape)}")
             desc[i, 0], desc[i, 1], desc[i, 2], desc[i, 3] = total, h, w, int(self.flips[i])
             total += h * w * 3
-        packed = torch.empty((total,), dtype=torch.uint8, pin_memory=True)
+        packed = torch.empty((total,), dtype=torch.uint8, pin_memory=pin)
         for i, frame in enumerate(self.frames):
             start = int(desc[i, 0])
             packed[start:start + frame.numel()].copy_(frame.reshape(-1))
+        self.packed, self.desc = packed, desc
+        if not keep_frames:
+            self.frames = []
+        return self
+
+    def __len__(self):
+        return int(self.shape[0])
+
+    def to(self, device, *_, **__):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise hip.MeError("StagedRaggedImages.to(): the batch is assembled by the HIP library - CUDA device required")
+        n = int(self.shape[0])
+        out = torch.empty(tuple(self.shape), device=device, dtype=torch.float32)
+        if n == 0:
+            return out
+        src = self if self.packed is not None else StagedRaggedImages(self.frames, self.size, self.flips).pack(pin=True)
+        packed, desc = src.packed, src.desc
+        total = int(packed.numel())
         d_src = packed.to(device, non_blocking=True)
         d_desc = desc.pin_memory().to(device, non_blocking=True)
         hip.check(hip.lib().me_image_batch_pad_resize_flip_u8_f32(d_src.data_ptr(), total, d_desc.data_ptr(), n,

@@ -72,16 +72,31 @@ def weights_init_normal(m):
         nn.init.kaiming_normal_(m.weight)
 
 
-def rescale_boxes(boxes, current_dim, original_shape):
-    """Undo pad-to-square + resize (reference :41-56); mutates and returns ``boxes`` (xyxy in the square frame ->
-    xyxy in the original ``(h, w)`` frame).  Per axis: ``((v - pad // 2) / unpadded) * original``."""
+def rescale_terms(current_dim, original_shape):
+    """Per axis the three python scalars of :func:`rescale_boxes`: ``{"x": (pad // 2, current_dim - pad, original), "y": ...}``
+    (reference :41-56).  The one place they are computed: ``rescale_boxes`` applies them with torch, :func:`rescale_scalars`
+    hands them to ``me_stream_tail_f32``."""
     orig = {"y": original_shape[0], "x": original_shape[1]}
     ratio = current_dim / max(original_shape)
     pad = {"x": max(orig["y"] - orig["x"], 0) * ratio, "y": max(orig["x"] - orig["y"], 0) * ratio}
+    return {axis: (pad[axis] // 2, current_dim - pad[axis], orig[axis]) for axis in ("x", "y")}
+
+
+def rescale_boxes(boxes, current_dim, original_shape):
+    """Undo pad-to-square + resize (reference :41-56); mutates and returns ``boxes`` (xyxy in the square frame ->
+    xyxy in the original ``(h, w)`` frame).  Per axis: ``((v - pad // 2) / unpadded) * original``."""
+    terms = rescale_terms(current_dim, original_shape)
     for col, axis in ((0, "x"), (1, "y"), (2, "x"), (3, "y")):
-        unpadded = current_dim - pad[axis]
-        boxes[:, col] = ((boxes[:, col] - pad[axis] // 2) / unpadded) * orig[axis]
+        half_pad, unpadded, original = terms[axis]
+        boxes[:, col] = ((boxes[:, col] - half_pad) / unpadded) * original
     return boxes
+
+
+def rescale_scalars(current_dim, frame_hw):
+    """The six float32 scalars per stream of ``me_stream_tail_f32`` as a ``[streams, 6]`` CPU tensor: :func:`rescale_terms`
+    for x, then for y, cast to float32 (the cast torch applies to a python scalar that meets a float32 tensor)."""
+    out = [[v for axis in ("x", "y") for v in rescale_terms(current_dim, hw)[axis]] for hw in frame_hw]
+    return torch.tensor(out, dtype=torch.float64).to(torch.float32).reshape(-1, 6)
 
 
 def _stack_last(parts, like):

@@ -7,7 +7,14 @@ host-side packing of the points and the copy are inside, so it bounds the launch
 generator call for one stream, and the host time of a step before its first network launch.  The "dark" rows feed 480x640
 frames that all select fusion (one ``Network.forward``, no gather); the "mixed" rows feed the tests' frames - two sizes, dark
 and bright interleaved - so that every step takes the mode split: two forwards on gathered sub-batches.  The radar streams and
-the float64 bar quoted in the first lines are those of tests/test_gpu_multistream.py (tests/multistream_helpers.py)."""
+the float64 bar quoted in the first lines are those of tests/test_gpu_multistream.py (tests/multistream_helpers.py).
+
+The output tail (``MultiStreamFuser(tail=...)``), both kinds in the same process, a block of each in every one of four repeats,
+the order alternating (host device, device host, ...): "tail
+alone" is ``_tail`` on the network's rows of one recorded step - from the device rows to the per-stream host rows, device
+synchronised - and "step" the whole step with either tail.  The last lines run the S = max row through
+``pipeline.FusionPipeline`` (two processes, every step inferred) against the in-process fuser: steps/s, the first step
+(spawn, rendezvous) left out."""
 import argparse
 import os
 import statistics
@@ -29,6 +36,33 @@ from tests.golden.make_golden import RADAR_CALIB, radar_points  # noqa: E402
 REPEATS = 3
 
 
+class DarkSource:
+    """Picklable source of the pipeline rows: ``steps`` steps of ``n`` dark 480x640 frames + the radar frames of ``main``."""
+
+    def __init__(self, steps, n):
+        self.steps, self.n = steps, n
+
+    def __call__(self):
+        frames = [(synth.uniform(f"ms/frame{s}", (480, 640, 3)) * 25).astype(np.uint8) for s in range(self.n)]
+        for f in range(self.steps):
+            yield frames, [[radar_points((f + 7 * s) % 45)] for s in range(self.n)]
+
+
+def timed_ab(fn_a, fn_b, steps, repeats=4):
+    """``timed`` for two variants, a block of each per repeat in alternating order (A B, B A, ...), so that both see the same
+    machine state and neither always runs first."""
+    a, b = [], []
+    for r in range(repeats):
+        for fn, out in (((fn_a, a), (fn_b, b)) if r % 2 == 0 else ((fn_b, b), (fn_a, a))):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for f in range(steps):
+                fn(f)
+            torch.cuda.synchronize()
+            out.append((time.perf_counter() - t0) / steps)
+    return statistics.median(a), statistics.median(b)
+
+
 def timed(fn, steps, repeats=REPEATS):
     out = []
     for _ in range(repeats):
@@ -47,6 +81,7 @@ def main():
     ap.add_argument("--streams", type=int, nargs="*", default=[1, 8, 32])
     ap.add_argument("--cfgs", nargs="*", default=["yolov3-tiny-12", "yolov3"])
     ap.add_argument("--out", default=None)
+    ap.add_argument("--no-pipeline", dest="pipeline", action="store_false", help="skip the two-process rows")
     args = ap.parse_args()
     lines = []
 
@@ -72,10 +107,13 @@ def main():
                 # the seeds wrap every 45 steps: the synthetic reflectors drift out of the filter's depth range after that, and
                 # seed 46 holds a point on the camera plane (tests/multistream_helpers.py)
                 radar = [[[radar_points((f + 7 * s) % 45)] for s in range(n)] for f in range(args.steps)]
-                multi = MultiStreamFuser(net, RADAR_CALIB, n, model_mode=3, min_hits=2)
+                multi = MultiStreamFuser(net, RADAR_CALIB, n, model_mode=3, min_hits=2)   # the default tail
+                other = MultiStreamFuser(net, RADAR_CALIB, n, model_mode=3, min_hits=2, tail="device" if multi.tail == "host" else "host")
+                multi_host, multi_dev = (multi, other) if multi.tail == "host" else (other, multi)
                 singles = [FrameFuser(net, RADAR_CALIB, model_mode=3, min_hits=2) for _ in range(n)]
                 for f in range(5):   # warm-up: plans, autotuner, allocator
                     multi(frames, radar[f])
+                    other(frames, radar[f])
                     for s in range(n):
                         singles[s](frames[s], radar[f][s])
                 t_multi = timed(lambda f: multi(frames, radar[f]), args.steps)
@@ -102,10 +140,39 @@ def main():
                     gen.heatmaps(32)
                     multi._modes(img)
                 t_front = timed(front, args.steps)
-                say(f"{cfg:16s} {dtype:4s} S={n:2d} {'mixed' if mixed else 'dark '}: multi {t_multi * 1e3:7.2f} ms/step "
+                say(f"{cfg:16s} {dtype:4s} S={n:2d} {'mixed' if mixed else 'dark '}: multi ({multi.tail} tail) {t_multi * 1e3:7.2f} ms/step "
                     f"({n / t_multi:7.1f} frames/s) | {n} x FrameFuser {t_seq * 1e3:7.2f} ms ({n / t_seq:7.1f} frames/s) | "
                     f"ratio {t_seq / t_multi:5.2f} | radar upload + proposal launches {t_launch:6.3f} ms | host generator, 1 stream "
                     f"{t_host_gen * 1e3:6.3f} ms | front before the network {t_front * 1e3:6.2f} ms")
+                # the output tail: both kinds on the rows of one recorded step, then the whole step with either
+                recorded = []
+                tail_fn = multi_dev._tail
+                multi_dev._tail = lambda rows, hws: recorded.append((rows.clone(), hws)) or tail_fn(rows, hws)
+                multi_dev(frames, radar[5])
+                multi_dev._tail = tail_fn
+                rows, hws = recorded[0]
+                t_tail_host, t_tail_dev = timed_ab(lambda f: multi_host._tail(rows, hws), lambda f: multi_dev._tail(rows, hws),
+                                                   args.steps)
+                t_step_host, t_step_dev = timed_ab(lambda f: multi_host(frames, radar[f]), lambda f: multi_dev(frames, radar[f]),
+                                                   args.steps)
+                say(f"{cfg:16s} {dtype:4s} S={n:2d} {'mixed' if mixed else 'dark '}: tail alone on {rows.shape[0]:5d} rows: host "
+                    f"{t_tail_host * 1e3:6.3f} ms, device {t_tail_dev * 1e3:6.3f} ms (x {t_tail_host / t_tail_dev:4.2f}) | step: "
+                    f"host tail {t_step_host * 1e3:7.2f} ms, device tail {t_step_dev * 1e3:7.2f} ms "
+                    f"({(t_step_dev / t_step_host - 1) * 100:+5.1f} %)")
+                if n == max(args.streams) and not mixed and args.pipeline:
+                    from millieye_amd.pipeline import FusionPipeline
+                    piped = MultiStreamFuser(net, RADAR_CALIB, n, model_mode=3, min_hits=2, tail="device")
+                    t0, done = None, 0
+                    for _results, _info in FusionPipeline(piped, DarkSource(args.steps + 1, n), skip_to_newest=False):
+                        if t0 is None:
+                            torch.cuda.synchronize()
+                            t0 = time.perf_counter()
+                        else:
+                            done += 1
+                    t_pipe = (time.perf_counter() - t0) / done
+                    say(f"{cfg:16s} {dtype:4s} S={n:2d} dark : two-process pipeline {1 / t_pipe:7.1f} steps/s ({t_pipe * 1e3:6.2f} ms/step) "
+                        f"| in-process fuser {1 / t_step_dev:7.1f} steps/s ({t_step_dev * 1e3:6.2f} ms/step) | ratio "
+                        f"{t_step_dev / t_pipe:4.2f}")
     if args.out:
         with open(args.out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
