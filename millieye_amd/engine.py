@@ -16,18 +16,21 @@ alive.  Here the cfg graph is compiled once per input shape into a short list of
 * each ``[yolo]`` decode writes its rows directly at its offset of the final
   ``[N, R, 5+C]`` tensor (no ``torch.cat``).
 
-Nothing in this file computes: it owns shapes, pointers and launch order.
+Nothing in this file computes: it owns shapes, pointers and launch order.  The graph logic of a plan - which blocks fuse,
+which activations share bytes - is ``planner.py`` (no torch, no library); ``DarknetEngine._build`` turns its result into
+descriptors.
 """
 import ctypes as C
+import json
 import os
+import time
 
 import torch
 
-from . import hip
+from . import hip, planner
+from .planner import pick_tap_module
 
 __all__ = ["DarknetEngine", "ConvWeights", "pick_tap_module", "invalidate_weights", "bump_versions"]
-
-_ALIGN = 256  # bytes
 
 # Packed-weight caches compare ``(data_ptr, _version)`` stamps.  Writers that bypass the version counter - reference-style
 # ``param.data.copy_()`` / ``.data.normal_()`` in user code, or a kernel writing through a raw pointer - call
@@ -46,35 +49,6 @@ def bump_versions(*tensors):
 
 _DTYPES = ("f32", "bf16", "f16")
 _TORCH_HALF = {"bf16": torch.bfloat16, "f16": torch.float16}
-
-
-def _resolve(idx, current):
-    """darknet layer reference -> absolute module index (negative = relative to ``current``)."""
-    idx = int(idx)
-    return current + idx if idx < 0 else idx
-
-
-def pick_tap_module(module_defs):
-    """Index of the module whose output is ``Darknet.featuremap``.
-
-    Reference rule (models.py:254-255): the ``nn.Sequential`` whose first child is named
-    ``conv_8`` - i.e. module 8 when it is convolutional (true for the tiny cfgs).  For cfgs where
-    module 8 is not a convolution (yolov3.cfg: a shortcut) the reference raises AttributeError;
-    documented extension: the last 256-filter convolution before the second
-    ``[yolo]`` block (yolov3.cfg module 91: 512->256 @ stride 16) - the only tensor compatible
-    with ``cnn_layers_1((256, 490))`` and ``spatial_scale = 1/16`` (my_models.py:427,495).
-    Returns ``None`` when no such module exists."""
-    if len(module_defs) > 8 and module_defs[8]["type"] == "convolutional":
-        return 8
-    yolos = [i for i, d in enumerate(module_defs) if d["type"] == "yolo"]
-    if len(yolos) < 2:
-        return None
-    tap = None
-    for i in range(yolos[0] + 1, yolos[1]):
-        d = module_defs[i]
-        if d["type"] == "convolutional" and int(d["filters"]) == 256:
-            tap = i
-    return tap
 
 
 class ConvWeights:
@@ -243,28 +217,21 @@ class ConvWeights:
         return "realloc" if realloc else True
 
 
-class _Tensor:
-    __slots__ = ("h", "w", "c", "parent", "chan_off", "producers", "readers", "offset", "pinned", "external", "esize",
-                 "padded")
+def _view(plan, tt):
+    """``(device pointer, pitch in elements)`` of a planned tensor inside the plan's arena."""
+    root, coff = tt.root()
+    return plan.arena.data_ptr() + root.offset + tt.esize * coff, root.c
 
-    def __init__(self, h, w, c, esize=4):
-        self.h, self.w, self.c = h, w, c
-        self.esize = esize    # bytes per element (4 = float32, 2 = bfloat16)
-        self.padded = 0       # zero channels appended behind the logical ones (bf16 mode, tiny cfgs' 16-channel stem)
-        self.parent = None
-        self.chan_off = 0
-        self.producers = []
-        self.readers = []
-        self.offset = None
-        self.pinned = False
-        self.external = False  # the network input (NCHW, caller owned)
 
-    def root(self):
-        t, off = self, 0
-        while t.parent is not None:
-            off += t.chan_off
-            t = t.parent
-        return t, off
+def _typed_view(plan, tt, nchw):
+    """torch view of an arena tensor ([n,h,w,c], or the NCHW permutation of it) - API boundary only"""
+    root, coff = tt.root()
+    n = plan.n
+    flat = plan.arena.view(_TORCH_HALF[plan.dtype] if tt.esize == 2 else torch.float32)
+    pitch, off = root.c, root.offset // tt.esize + coff
+    if nchw:
+        return torch.as_strided(flat, (n, tt.c, tt.h, tt.w), (tt.h * tt.w * pitch, 1, tt.w * pitch, pitch), off)
+    return torch.as_strided(flat, (n, tt.h, tt.w, tt.c), (tt.h * tt.w * pitch, tt.w * pitch, pitch, 1), off)
 
 
 class _Plan:
@@ -308,7 +275,6 @@ class DarknetEngine:
         gradient ride along, except for layer 0 (no data gradient) and the 3x3 / stride-2 layers (their data gradient is the
         output-parity convolution built from the forward layout).  Falls back to the per-layer launches when a block is not
         plain fp32 on ``device``."""
-        import ctypes as C
         dev = torch.device(device)
         if dev.type == "cuda" and dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
@@ -409,356 +375,153 @@ class DarknetEngine:
 
     # ---------------------------------------------------------------------------------- planning
     def _build(self, n, h, w, device, keep_raw=False):
-        defs = self.model.module_defs
-        L = len(defs)
-        hyper_c = int(self.model.hyperparams["channels"])
-
-        # who reads layer k?
-        readers = [[] for _ in range(L)]
-        srcs = [None] * L
-        for i, d in enumerate(defs):
-            t = d["type"]
-            if t in ("convolutional", "upsample", "maxpool", "yolo"):
-                srcs[i] = [i - 1]
-            elif t == "route":
-                srcs[i] = [_resolve(x, i) for x in d["layers"].split(",")]
-            elif t == "shortcut":
-                srcs[i] = [i - 1, _resolve(d["from"], i)]
-            else:
-                raise ValueError(f"unsupported cfg block [{t}] at module {i}")
-            for s in srcs[i]:
-                if s >= 0:
-                    readers[s].append(i)
-        tap = self.tap_module
-
-        tensors = []
-        bf16 = self.dtype in _TORCH_HALF  # any 16-bit storage mode
-        half_type = hip.HALF_TYPES[_TORCH_HALF[self.dtype]] if bf16 else 0
-        if bf16 and keep_raw:
-            raise NotImplementedError("a 16-bit ENGINE PLAN keeps no raw maps (the loss value of an evaluation call comes from the fp32 engine; "
-                                      "training in a 16-bit storage mode is millieye_amd/detector_train16.py, not an engine plan)")
-        act_esize = 2 if bf16 else 4
-
-        def new_tensor(hh, ww, cc, esize=None):
-            t = _Tensor(hh, ww, cc, act_esize if esize is None else esize)
-            tensors.append(t)
-            return t
-
-        def feeds_yolo_only(idx):
-            return bool(readers[idx]) and all(defs[r]["type"] == "yolo" for r in readers[idx])
-
-        t_in = new_tensor(h, w, hyper_c, 4)
-        t_in.external = True
-        out = [None] * L  # layer index -> _Tensor
-        ops = []  # dicts
-        fused_away = set()
-        yolo_rows = []
-        i = 0
-        while i < L:
-            d = defs[i]
-            t = d["type"]
-            if t == "convolutional":
-                x = t_in if i == 0 else out[i - 1]
-                if x is None:
-                    raise RuntimeError(f"module {i} reads a fused-away tensor")
-                k, s = int(d["size"]), int(d["stride"])
-                pad = (k - 1) // 2
-                cout = int(d["filters"])
-                ho = (x.h + 2 * pad - k) // s + 1
-                wo = (x.w + 2 * pad - k) // s + 1
-                act = hip.ACT_LEAKY if d["activation"] == "leaky" else hip.ACT_LINEAR
-                op = dict(kind="conv", module=i, x=x, res=None, k=k, s=s, pad=pad, act=act, ups=1, ho=ho, wo=wo,
-                          cout=cout)
-                y_esize, y_c = act_esize, cout
-                if bf16:
-                    if x.esize != (4 if x.external else 2):
-                        raise RuntimeError(f"module {i}: a convolution reads an fp32 detection map in bf16 mode")
-                    if feeds_yolo_only(i):
-                        y_esize = 4   # raw detection maps stay fp32 for the YOLO decode
-                    elif cout % 32:
-                        y_c = -(-cout // 32) * 32  # the next MFMA conv needs cin % 32 == 0: zero channels behind the real ones
-                nxt = defs[i + 1] if i + 1 < L else None
-                only_next = readers[i] == [i + 1] and i != tap
-                if (nxt is not None and nxt["type"] == "shortcut" and only_next and x.c > 4
-                        and srcs[i + 1][0] == i and out[srcs[i + 1][1]] is not None
-                        and srcs[i + 1][1] != i):
-                    res = out[srcs[i + 1][1]]
-                    if (res.h, res.w, res.c) == (ho, wo, cout) and y_c == cout and y_esize == res.esize:
-                        y = new_tensor(ho, wo, cout, y_esize)
-                        op["res"] = res
-                        op["y"] = y
-                        op["covers"] = (i, i + 1)
-                        out[i + 1] = y
-                        fused_away.add(i)
-                        ops.append(op)
-                        i += 2
-                        continue
-                if (nxt is not None and nxt["type"] == "upsample" and int(nxt["stride"]) == 2 and only_next
-                        and x.c > 4 and y_c == cout):
-                    y = new_tensor(ho * 2, wo * 2, cout, y_esize)
-                    op["ups"] = 2
-                    op["y"] = y
-                    op["covers"] = (i, i + 1)
-                    out[i + 1] = y
-                    fused_away.add(i)
-                    ops.append(op)
-                    i += 2
-                    continue
-                y = new_tensor(ho, wo, y_c, y_esize)
-                y.padded = y_c - cout
-                op["y"] = y
-                op["covers"] = (i,)
-                out[i] = y
-                ops.append(op)
-            elif t == "maxpool":
-                x = out[i - 1]
-                k, s = int(d["size"]), int(d["stride"])
-                zero_ext = (k == 2 and s == 1)
-                pad = (k - 1) // 2
-                ext = 1 if zero_ext else 0
-                ho = (x.h + ext + 2 * pad - k) // s + 1
-                wo = (x.w + ext + 2 * pad - k) // s + 1
-                y = new_tensor(ho, wo, x.c, x.esize)
-                y.padded = x.padded
-                ops.append(dict(kind="pool", module=i, x=x, y=y, k=k, s=s, pad=pad, zero_ext=ext, ho=ho, wo=wo))
-                out[i] = y
-            elif t == "upsample":
-                x = out[i - 1]
-                f = int(d["stride"])
-                y = new_tensor(x.h * f, x.w * f, x.c, x.esize)
-                y.padded = x.padded
-                ops.append(dict(kind="upsample", module=i, x=x, y=y, f=f))
-                out[i] = y
-            elif t == "shortcut":
-                a, b = out[srcs[i][0]], out[srcs[i][1]]
-                if a.esize != b.esize or a.padded or b.padded:
-                    raise NotImplementedError(f"shortcut {i}: mixed storage types / padded channels")
-                y = new_tensor(a.h, a.w, a.c, a.esize)
-                ops.append(dict(kind="add", module=i, a=a, b=b, y=y))
-                out[i] = y
-            elif t == "route":
-                parts = [out[s] for s in srcs[i]]
-                if any(p is None for p in parts):
-                    raise RuntimeError(f"route {i} reads a fused-away tensor")
-                if len(parts) == 1:
-                    out[i] = parts[0]
-                else:
-                    if any(p.padded or p.esize != parts[0].esize for p in parts):
-                        raise NotImplementedError(f"route {i}: mixed storage types / padded channels")
-                    cat = new_tensor(parts[0].h, parts[0].w, sum(p.c for p in parts), parts[0].esize)
-                    off = 0
-                    for p in parts:
-                        if (p.h, p.w) != (cat.h, cat.w):
-                            raise ValueError(f"route {i}: spatial size mismatch")
-                        if p.parent is None and not p.external and p is not cat and not _in_family(cat, p):
-                            p.parent, p.chan_off = cat, off
-                        else:  # already part of another concat: materialise a copy
-                            piece = new_tensor(p.h, p.w, p.c, p.esize)
-                            piece.parent, piece.chan_off = cat, off
-                            ops.append(dict(kind="copy", module=i, x=p, y=piece))
-                        off += p.c
-                    out[i] = cat
-            elif t == "yolo":
-                x = out[i - 1]
-                if x.h != x.w or h != w:
-                    raise ValueError("YOLO decode needs square inputs (the reference uses one grid_size)")
-                yl = self.model.module_list[i][0]
-                na, nc = yl.num_anchors, yl.num_classes
-                if x.c != na * (nc + 5):
-                    raise ValueError(f"yolo {i}: {x.c} channels != {na}*({nc}+5)")
-                if x.esize != 4:
-                    raise RuntimeError(f"yolo {i}: the detection map is shared with another reader (bf16 mode)")
-                ops.append(dict(kind="yolo", module=i, x=x, layer=yl, g=x.h, row_offset=sum(yolo_rows)))
-                yolo_rows.append(na * x.h * x.h)
-                out[i] = None  # decoded rows are never routed
-            i += 1
-
-        # the [yolo] decodes go behind the last convolution: one launch for all scales (me_yolo_decode_cand_multi_f32) instead of
-        # three small ones in the middle of the dependent chain; the detection maps stay live until then (liveness below)
-        if os.environ.get("MILLIEYE_DECODE_LAST", "1") != "0":
-            ops = [op for op in ops if op["kind"] != "yolo"] + [op for op in ops if op["kind"] == "yolo"]
-
-        # liveness (op index granularity)
-        for oi, op in enumerate(ops):
-            for key in ("x", "res", "a", "b"):
-                tt = op.get(key)
-                if tt is not None:
-                    tt.readers.append(oi)
-            if op.get("y") is not None:
-                op["y"].producers.append(oi)
-        tap_tensor = out[tap] if tap is not None and tap < L else None
-        if tap_tensor is not None:
-            tap_tensor.pinned = True
-        if keep_raw:  # the YOLO loss reads the raw detection maps after the run: exempt them from reuse
-            for op in ops:
-                if op["kind"] == "yolo":
-                    op["x"].pinned = True
-
-        fam = {}
-        for tt in tensors:
-            if tt.external:
-                continue
-            root, _ = tt.root()
-            first, last, pin = fam.get(id(root), (10 ** 9, -1, False))
-            if tt.producers:
-                first = min(first, min(tt.producers))
-            if tt.readers:
-                last = max(last, max(tt.readers))
-            pin = pin or tt.pinned
-            fam[id(root)] = (first, last, pin)
-        roots = []
-        for tt in tensors:
-            if tt.external or tt.parent is not None or id(tt) not in fam:
-                continue
-            first, last, pin = fam[id(tt)]
-            if first == 10 ** 9:
-                continue  # never produced (should not happen)
-            if pin:
-                last = len(ops)
-            last = max(last, first)
-            size = -(-(n * tt.h * tt.w * tt.c * tt.esize) // _ALIGN) * _ALIGN  # bytes
-            roots.append((first, last, size, tt))
-        roots.sort(key=lambda r: (r[0], -r[2]))
-        placed = []  # (offset, size, first, last)
-        total = 0
-        for first, last, size, tt in roots:
-            busy = sorted((o, s) for (o, s, f, l) in placed if not (l < first or f > last))
-            off = 0
-            for o, s in busy:
-                if off + size <= o:
-                    break
-                off = max(off, o + s)
-            tt.offset = off
-            placed.append((off, size, first, last))
-            total = max(total, off + size)
+        """Plan of one input shape: lower the cfg graph and place its tensors (millieye_amd/planner.py - pure, CPU-tested), then
+        allocate the arena, fill the launch descriptors, attach the scratch buffers and let the measured choices in."""
+        defs, tap = self.model.module_defs, self.tap_module
+        half = self.dtype in _TORCH_HALF  # any 16-bit storage mode
+        ops, tensors, out, yolo_rows = planner.lower(defs, int(self.model.hyperparams["channels"]), h, w, tap, half, keep_raw,
+                                                     decode_last=os.environ.get("MILLIEYE_DECODE_LAST", "1") != "0")
+        tap_tensor = out[tap] if tap is not None and tap < len(defs) else None
+        total = planner.place(ops, tensors, n, tap_tensor, keep_raw)
 
         plan = _Plan()
         plan.n, plan.h, plan.w = n, h, w
-        plan.arena = torch.empty(max(total, _ALIGN), dtype=torch.uint8, device=device)
-        if plan.arena.data_ptr() % _ALIGN:
+        plan.arena = torch.empty(max(total, planner._ALIGN), dtype=torch.uint8, device=device)
+        if plan.arena.data_ptr() % planner._ALIGN:
             raise RuntimeError("the caching allocator returned an arena that is not 256-byte aligned")
         plan.arena_bytes = total
         plan.dtype = self.dtype
         plan.rows = sum(yolo_rows)
-        plan.num_classes = None
-        base = plan.arena.data_ptr()
-
-        def view(tt):
-            root, coff = tt.root()
-            return base + root.offset + tt.esize * coff, root.c
-
-        def typed_view(tt, nchw):
-            """torch view of an arena tensor ([n,h,w,c], or the NCHW permutation of it) - API boundary only"""
-            root, coff = tt.root()
-            flat = plan.arena.view(_TORCH_HALF[self.dtype] if tt.esize == 2 else torch.float32)
-            pitch, off = root.c, root.offset // tt.esize + coff
-            if nchw:
-                return torch.as_strided(flat, (n, tt.c, tt.h, tt.w), (tt.h * tt.w * pitch, 1, tt.w * pitch, pitch), off)
-            return torch.as_strided(flat, (n, tt.h, tt.w, tt.c), (tt.h * tt.w * pitch, tt.w * pitch, pitch, 1), off)
-
         lib = hip.lib()
-        launches = []
+        self._emit(plan, ops, device, lib)
+        self._attach_workspace(plan, device, lib)
+        if _autotune_enabled():
+            _autotune(plan, lib)
+        plan.fused_blocks = []
+        if half and _bneck_mode() != "0" and (_autotune_enabled() or _bneck_mode() == "force"):
+            _fuse_bottlenecks(plan, ops, lib)   # (a measured choice, like the tiles: not without the autotuner - pinned plans stay pinned)
+        if tap_tensor is not None:
+            # NCHW view of the feature tap in its storage type (bf16 mode: callers that need fp32 convert at the API
+            # boundary - Darknet.forward; Network.forward hands the bf16 tap straight to the score-map conv)
+            plan.tap = _typed_view(plan, tap_tensor, nchw=True)
+            plan.tap_ptr, plan.tap_pitch = _view(plan, tap_tensor)
+            plan.tap_shape = (tap_tensor.h, tap_tensor.w, tap_tensor.c)
+        else:
+            plan.tap = None
+        return plan
+
+    def _emit(self, plan, ops, device, lib):
+        """One launch ``(function, arguments, descriptor or None, name)`` per op, pointers and pitches from the placed tensors."""
+        n, half = plan.n, plan.dtype in _TORCH_HALF
+        half_type = hip.HALF_TYPES[_TORCH_HALF[plan.dtype]] if half else 0
+        plan.num_classes = None
         plan.input_descs = []
         plan.yolo_raw = []  # raw detection maps [n,g,g,A*(5+C)] (arena views) for the YOLO loss
         plan.yolo_descs = []
         plan.conv_descs = []
-        flops = 0
+        plan.conv_flops = 0
+        plan.launches = launches = []
         for op in ops:
-            kind = op["kind"]
+            kind, x, y, dsc = op["kind"], op.get("x"), op.get("y"), None
             if kind == "conv":
-                x, y = op["x"], op["y"]
-                cw = self._conv_weights(op["module"], x.c if x.padded else 0, y.c if y.padded else 0)
-                if cw.refresh(device) == "realloc" and self._plans:
-                    self._plans.clear()
-                dsc = hip.Conv16Desc() if bf16 else hip.ConvDesc()
-                if x.external:
-                    dsc.x, dsc.x_pitch, dsc.x_nchw = None, x.c, 1
-                    plan.input_descs.append(dsc)
-                else:
-                    dsc.x, dsc.x_pitch = view(x)
-                    dsc.x_nchw = 0
-                dsc.wgt, dsc.scale, dsc.shift = cw.wgt.data_ptr(), cw.scale.data_ptr(), cw.shift.data_ptr()
-                if op["res"] is not None:
-                    dsc.res, dsc.res_pitch = view(op["res"])
-                else:
-                    dsc.res, dsc.res_pitch = None, 0
-                dsc.y, dsc.y_pitch = view(y)
-                dsc.n, dsc.h, dsc.w, dsc.cin = n, x.h, x.w, x.c
-                dsc.cout, dsc.ksize, dsc.stride, dsc.pad = cw.wgt.shape[0], op["k"], op["s"], op["pad"]
-                dsc.ho, dsc.wo, dsc.act, dsc.upsample, dsc.tile = op["ho"], op["wo"], op["act"], op["ups"], 0
-                dsc.split_k, dsc.workspace, dsc.workspace_bytes = 0, None, 0
-                dsc.wgt_tiled = cw.wgt_tiled.data_ptr() if cw.wgt_tiled is not None else None
-                if bf16:
-                    dsc.y_f32 = 1 if y.esize == 4 else 0
-                    dsc.half_type = half_type
                 op["launch"] = len(launches)
-                op["desc"] = dsc
-                launches.append((lib.me_conv2d_h16 if bf16 else lib.me_conv2d_f32, (C.byref(dsc),), dsc,
-                                 f"conv{op['module']}"))
-                plan.conv_descs.append((op["module"], dsc))
-                flops += 2 * n * op["ho"] * op["wo"] * op["cout"] * op["k"] * op["k"] * (x.c - x.padded)
-            elif kind == "pool" and bf16:
-                x, y = op["x"], op["y"]
-                (xp, xpitch), (yp, ypitch) = view(x), view(y)
-                launches.append((lib.me_maxpool_h16,
-                                 (xp, xpitch, yp, ypitch, n, x.h, x.w, x.c, op["k"], op["s"],
-                                  0 if op["zero_ext"] else op["pad"], op["zero_ext"], op["ho"], op["wo"], half_type), None,
-                                 f"pool{op['module']}"))
+                dsc = op["desc"] = self._conv_desc(plan, op, device, half_type)
+                fn = lib.me_conv2d_h16 if half else lib.me_conv2d_f32
+            elif kind == "pool" and half:
+                fn = lib.me_maxpool_h16
+                args = (*_view(plan, x), *_view(plan, y), n, x.h, x.w, x.c, op["k"], op["s"],
+                        0 if op["zero_ext"] else op["pad"], op["zero_ext"], op["ho"], op["wo"], half_type)
             elif kind == "pool":
-                x, y = op["x"], op["y"]
                 dsc = hip.PoolDesc()
-                dsc.x, dsc.x_pitch = view(x)
-                dsc.y, dsc.y_pitch = view(y)
+                dsc.x, dsc.x_pitch = _view(plan, x)
+                dsc.y, dsc.y_pitch = _view(plan, y)
                 dsc.n, dsc.h, dsc.w, dsc.c = n, x.h, x.w, x.c
                 dsc.size, dsc.stride, dsc.pad, dsc.zero_ext = op["k"], op["s"], (0 if op["zero_ext"] else op["pad"]), \
                     op["zero_ext"]
                 dsc.ho, dsc.wo = op["ho"], op["wo"]
-                launches.append((lib.me_maxpool_f32, (C.byref(dsc),), dsc, f"pool{op['module']}"))
+                fn = lib.me_maxpool_f32
             elif kind == "upsample":
-                x, y = op["x"], op["y"]
-                (xp, xpitch), (yp, ypitch) = view(x), view(y)
-                launches.append((lib.me_upsample_h16 if x.esize == 2 else lib.me_upsample_f32,
-                                 (xp, xpitch, yp, ypitch, n, x.h, x.w, x.c, op["f"]), None,
-                                 f"upsample{op['module']}"))
+                fn = lib.me_upsample_h16 if x.esize == 2 else lib.me_upsample_f32
+                args = (*_view(plan, x), *_view(plan, y), n, x.h, x.w, x.c, op["f"])
             elif kind == "add":
-                a, b, y = op["a"], op["b"], op["y"]
-                (ap, apitch), (bp, bpitch), (yp, ypitch) = view(a), view(b), view(y)
-                launches.append((lib.me_add_h16 if a.esize == 2 else lib.me_add_f32,
-                                 (ap, apitch, bp, bpitch, yp, ypitch, n * a.h * a.w, a.c)
-                                 + ((half_type,) if a.esize == 2 else ()), None,
-                                 f"add{op['module']}"))
+                a = op["a"]
+                fn = lib.me_add_h16 if a.esize == 2 else lib.me_add_f32
+                args = (*_view(plan, a), *_view(plan, op["b"]), *_view(plan, y), n * a.h * a.w, a.c) \
+                    + ((half_type,) if a.esize == 2 else ())
             elif kind == "copy":
-                x, y = op["x"], op["y"]
-                (xp, xpitch), (yp, ypitch) = view(x), view(y)
-                launches.append((lib.me_copy_h16 if x.esize == 2 else lib.me_copy_f32,
-                                 (xp, xpitch, yp, ypitch, n * x.h * x.w, x.c), None,
-                                 f"copy{op['module']}"))
+                fn = lib.me_copy_h16 if x.esize == 2 else lib.me_copy_f32
+                args = (*_view(plan, x), *_view(plan, y), n * x.h * x.w, x.c)
             elif kind == "yolo":
-                x, yl = op["x"], op["layer"]
-                dsc = hip.YoloDesc()
-                dsc.x, dsc.x_pitch = view(x)
-                dsc.out = None
-                dsc.n, dsc.g, dsc.num_anchors, dsc.num_classes = n, op["g"], yl.num_anchors, yl.num_classes
-                dsc.rows_total, dsc.row_offset = plan.rows, op["row_offset"]
-                stride = h / op["g"]
-                dsc.stride = stride
-                for k, (aw, ah) in enumerate(yl.anchors):
-                    dsc.anchors[2 * k] = aw / stride
-                    dsc.anchors[2 * k + 1] = ah / stride
-                plan.num_classes = yl.num_classes
-                plan.yolo_descs.append(dsc)
-                plan.yolo_raw.append(typed_view(x, nchw=False))
-                launches.append((lib.me_yolo_decode_f32, (C.byref(dsc),), dsc, f"yolo{op['module']}"))
-                # side effects the reference's YOLOLayer.forward has (models.py:135-156)
-                yl.img_dim = h
-                yl.grid_size = op["g"]
-                yl.stride = stride
+                dsc = self._yolo_desc(plan, op)
+                fn = lib.me_yolo_decode_f32
+            launches.append((fn, args if dsc is None else (C.byref(dsc),), dsc, f"{kind}{op['module']}"))
         k = len(plan.yolo_descs)
         plan.yolo_tail = None  # the decodes are the last launches: Network.forward's candidate-list decode takes them in one launch
         if 1 <= k <= 3 and all(name.startswith("yolo") for _f, _a, _k, name in launches[-k:]):
             plan.yolo_tail = (C.c_void_p * k)(*[C.addressof(dsc) for dsc in plan.yolo_descs])
+
+    def _conv_desc(self, plan, op, device, half_type):
+        x, y = op["x"], op["y"]
+        half = plan.dtype in _TORCH_HALF
+        cw = self._conv_weights(op["module"], x.c if x.padded else 0, y.c if y.padded else 0)
+        if cw.refresh(device) == "realloc" and self._plans:
+            self._plans.clear()
+        dsc = hip.Conv16Desc() if half else hip.ConvDesc()
+        if x.external:
+            dsc.x, dsc.x_pitch, dsc.x_nchw = None, x.c, 1
+            plan.input_descs.append(dsc)
+        else:
+            dsc.x, dsc.x_pitch = _view(plan, x)
+            dsc.x_nchw = 0
+        dsc.wgt, dsc.scale, dsc.shift = cw.wgt.data_ptr(), cw.scale.data_ptr(), cw.shift.data_ptr()
+        if op["res"] is not None:
+            dsc.res, dsc.res_pitch = _view(plan, op["res"])
+        else:
+            dsc.res, dsc.res_pitch = None, 0
+        dsc.y, dsc.y_pitch = _view(plan, y)
+        dsc.n, dsc.h, dsc.w, dsc.cin = plan.n, x.h, x.w, x.c
+        dsc.cout, dsc.ksize, dsc.stride, dsc.pad = cw.wgt.shape[0], op["k"], op["s"], op["pad"]
+        dsc.ho, dsc.wo, dsc.act, dsc.upsample, dsc.tile = op["ho"], op["wo"], op["act"], op["ups"], 0
+        dsc.split_k, dsc.workspace, dsc.workspace_bytes = 0, None, 0
+        dsc.wgt_tiled = cw.wgt_tiled.data_ptr() if cw.wgt_tiled is not None else None
+        if half:
+            dsc.y_f32 = 1 if y.esize == 4 else 0
+            dsc.half_type = half_type
+        plan.conv_descs.append((op["module"], dsc))
+        plan.conv_flops += 2 * plan.n * op["ho"] * op["wo"] * op["cout"] * op["k"] * op["k"] * (x.c - x.padded)
+        return dsc
+
+    def _yolo_desc(self, plan, op):
+        x, i = op["x"], op["module"]
+        yl = self.model.module_list[i][0]
+        na, nc = yl.num_anchors, yl.num_classes
+        if x.c != na * (nc + 5):
+            raise ValueError(f"yolo {i}: {x.c} channels != {na}*({nc}+5)")
+        dsc = hip.YoloDesc()
+        dsc.x, dsc.x_pitch = _view(plan, x)
+        dsc.out = None
+        dsc.n, dsc.g, dsc.num_anchors, dsc.num_classes = plan.n, op["g"], na, nc
+        dsc.rows_total, dsc.row_offset = plan.rows, op["row_offset"]
+        stride = plan.h / op["g"]
+        dsc.stride = stride
+        for k, (aw, ah) in enumerate(yl.anchors):
+            dsc.anchors[2 * k] = aw / stride
+            dsc.anchors[2 * k + 1] = ah / stride
+        plan.num_classes = nc
+        plan.yolo_descs.append(dsc)
+        plan.yolo_raw.append(_typed_view(plan, x, nchw=False))
+        # side effects the reference's YOLOLayer.forward has (models.py:135-156)
+        yl.img_dim = plan.h
+        yl.grid_size = op["g"]
+        yl.stride = stride
+        return dsc
+
+    @staticmethod
+    def _attach_workspace(plan, device, lib):
+        """Scratch shared by the convolutions of a plan: the split-K slabs and (opt-in) the in-launch reduction's counters."""
+        half = plan.dtype in _TORCH_HALF
         # shared scratch for the deterministic split-K slabs (launches are serial on one stream)
-        ws_fn = lib.me_conv2d_h16_workspace_bytes if bf16 else lib.me_conv2d_workspace_bytes
+        ws_fn = lib.me_conv2d_h16_workspace_bytes if half else lib.me_conv2d_workspace_bytes
         need = max([ws_fn(C.byref(d)) for _m, d in plan.conv_descs] + [0])
         # arrival counters of the in-launch split-K reduction (zero between launches; one array per plan = per stream).  Opt-in:
         # on MI355X the serial tail of the last workgroup (drain, ticket, slab reads past the L2) costs more than the launch it
@@ -777,22 +540,6 @@ class DarknetEngine:
             for _m, d in plan.conv_descs:
                 if ws_fn(C.byref(d)) > 0:
                     d.workspace, d.workspace_bytes = ws_ptr, need
-        plan.launches = launches
-        plan.conv_flops = flops
-        if _autotune_enabled():
-            _autotune(plan, lib)
-        plan.fused_blocks = []
-        if bf16 and _bneck_mode() != "0" and (_autotune_enabled() or _bneck_mode() == "force"):
-            _fuse_bottlenecks(plan, ops, lib)   # (a measured choice, like the tiles: not without the autotuner - pinned plans stay pinned)
-        if tap_tensor is not None:
-            # NCHW view of the feature tap in its storage type (bf16 mode: callers that need fp32 convert at the API
-            # boundary - Darknet.forward; Network.forward hands the bf16 tap straight to the score-map conv)
-            plan.tap = typed_view(tap_tensor, nchw=True)
-            plan.tap_ptr, plan.tap_pitch = view(tap_tensor)
-            plan.tap_shape = (tap_tensor.h, tap_tensor.w, tap_tensor.c)
-        else:
-            plan.tap = None
-        return plan
 
     def plan_for(self, x, keep_raw=False):
         n, _, h, w = x.shape
@@ -962,7 +709,6 @@ def _graphs_enabled():
     """Opt-in (``MILLIEYE_HIPGRAPH=1``, or inside ``graph_replay()``).  Measured on MI355X (Darknet-53 @416): 655 vs 661 frames/s at
     batch 1, 1508 vs 1514 at batch 8 with / without the graph - the GPU side of the path is bound by the kernels' own latency, not by
     launches, so the eager sequence stays the default."""
-    import os
     return getattr(_GRAPH_SCOPE, "depth", 0) > 0 or os.environ.get("MILLIEYE_HIPGRAPH", "0") in ("1", "true", "on")
 
 
@@ -1003,12 +749,10 @@ _SPECULATIVE = os.environ.get("MILLIEYE_CHECK_FIRST", "0") != "1"  # (=1: parame
 
 
 def _autotune_enabled():
-    import os
     return os.environ.get("MILLIEYE_AUTOTUNE", "1") not in ("0", "false", "off")
 
 
 def _tune_file():
-    import os
     path = os.environ.get("MILLIEYE_TUNE_CACHE")
     if path:
         return path
@@ -1017,8 +761,6 @@ def _tune_file():
 
 
 def _tune_load():
-    import json
-    import os
     if _TUNE_FILE_LOADED[0]:
         return
     _TUNE_FILE_LOADED[0] = True
@@ -1031,8 +773,6 @@ def _tune_load():
 
 
 def _tune_save():
-    import json
-    import os
     path = _tune_file()
     try:
         os.makedirs(os.path.dirname(path), exist_ok=True)
@@ -1050,8 +790,6 @@ def _autotune(plan, lib):
     best on average but misjudges the wave-quantisation of individual layers; measuring is cheap (about a
     second per plan, outside any timed region) and cached per layer shape for the life of the process.
     Every candidate computes the same convolution (parity tests cover all tiles and split-K)."""
-    import os
-    import time
 
     stream = hip.stream_ptr()
     _tune_load()
@@ -1259,7 +997,6 @@ def _fuse_bottlenecks(plan, ops, lib):
     csrc/bneck_h16.hip; reference yolov3/models.py:22-41, 258-260 - the residual blocks of yolov3.cfg).  Same rounding points
     as the pair; which of the two forms runs is decided by MEASUREMENT per block shape (the pair with its tuned tiles against
     every instance of the one-launch kernel, interleaved, HIP events on the launch stream), cached for the life of the process."""
-    import time
     stream = hip.stream_ptr()
     launches = plan.launches
     conv_ops = [op for op in ops if op["kind"] == "conv"]
@@ -1346,13 +1083,3 @@ def _fuse_bottlenecks(plan, ops, lib):
         launches[b["launch"]] = None
         plan.fused_blocks.append((a["module"], b["module"], int(choice)))
     plan.launches = [entry for entry in launches if entry is not None]
-
-
-def _in_family(cat, p):
-    """True if ``cat`` is (transitively) a slice of ``p`` - guards against cyclic concat parents."""
-    t = cat
-    while t is not None:
-        if t is p:
-            return True
-        t = t.parent
-    return False

@@ -103,17 +103,23 @@ def test_darknet_weights_roundtrip(tmp_path):
 
 def test_engine_plan_fuses_and_reuses_memory():
     """Planning is pure host logic: no GPU, no library call."""
-    from millieye_amd.engine import DarknetEngine, pick_tap_module
-    v3 = ph.make_darknet("yolov3")
-    eng = DarknetEngine(v3)
-    assert pick_tap_module(v3.module_defs) == 91
-    # drive only the symbolic part of _build by stubbing hip.lib / weights
-    defs = v3.module_defs
-    fused = 0
-    for i, d in enumerate(defs[:-1]):
-        if d["type"] == "convolutional" and defs[i + 1]["type"] in ("shortcut", "upsample"):
-            fused += 1
-    assert fused == 23 + 2  # every [shortcut] and [upsample] of yolov3.cfg sits right after a conv
+    from millieye_amd import planner
+    from millieye_amd.engine import pick_tap_module
+    from millieye_amd.utils.parse_config import parse_model_config
+    defs = parse_model_config(ph.cfg_path("yolov3"))[1:]
+    tap = pick_tap_module(defs)
+    assert tap == 91
+    n = 2
+    ops, tensors, out, _rows = planner.lower(defs, 3, 96, 96, tap, False, False)
+    # every [shortcut] and [upsample] of yolov3.cfg sits right after a conv and rides in its epilogue
+    fused = [op for op in ops if op["kind"] == "conv" and op["covers"] == (op["module"], op["module"] + 1)]
+    assert sum(op["res"] is not None and op["ups"] == 1 for op in fused) == 23
+    assert sum(op["ups"] == 2 and op["res"] is None for op in fused) == 2 and len(fused) == 25
+    assert not any(op["kind"] in ("add", "upsample") for op in ops)
+    arena_bytes = planner.place(ops, tensors, n, out[tap], False)
+    roots = [t for t in tensors if not t.external and t.parent is None]
+    assert all(t.offset is not None for t in roots)
+    assert 0 < arena_bytes < sum(n * t.h * t.w * t.c * t.esize for t in roots)
 
 
 def test_synth_is_deterministic_and_sane():
