@@ -679,7 +679,8 @@ int me_radar_heatmap_f32(const double* points, const int32_t* offsets, const int
 #define ME_RADAR_OK 0
 #define ME_RADAR_E_POINTS 1   /* more than ME_RADAR_MAX_POINTS points pass the filter            */
 #define ME_RADAR_E_CLUSTERS 2 /* more than ME_RADAR_MAX_CLUSTERS clusters pass the num_pts filter */
-#define ME_RADAR_E_TRACKS 3   /* old tracks + unmatched clusters exceed ME_RADAR_MAX_TRACKS       */
+#define ME_RADAR_E_TRACKS 3   /* old tracks + unmatched clusters exceed ME_RADAR_MAX_TRACKS: cannot occur while
+                               * MAX_CLUSTERS <= MAX_TRACKS (the sum is max(tracks, clusters)); kept as a guard */
 #define ME_RADAR_E_COST 4     /* the association cost is not finite (scipy raises ValueError)     */
 typedef struct me_radar_desc {
   const double* points;

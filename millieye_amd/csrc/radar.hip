@@ -8,8 +8,8 @@
 //   radar_pack_kernel    slots -> the packed [total,5] boxes of Network.forward and the packed (points, offsets) of
 //                        me_radar_heatmap_f32.
 //   frame_means_kernel   one mean per frame (the auto mode's img.mean()).
-// Nothing here is throughput-bound (about 25 points, 3 clusters, 4 tracks per stream); the point is that S streams cost two
-// launches and no host loop.
+// Nothing here is throughput-bound (the demos have about 25 points, 3 clusters, 4 tracks per stream; tests/test_gpu_radar_chain.py
+// runs it at the capacities, 256 / 32 / 32); the point is that S streams cost two launches and no host loop.
 #include <stddef.h>
 
 #include "common.h"
@@ -373,6 +373,8 @@ __global__ __launch_bounds__(THREADS) void radar_chain_kernel(me_radar_desc d) {
       }
       for (int j = 0; j < nclu; ++j)
         if (s_m_new[j] < 0) s_newlist[n_new++] = j;
+      // A complete rectangular assignment leaves max(0, nclu - T) clusters unmatched, so T + n_new = max(T, nclu) <= 32 while
+      // MAXC <= MAXT: this cannot fire.  It guards the appends below against a change of the capacities.
       if (T + n_new > MAXT) s_status = ME_RADAR_E_TRACKS;
     }
     s_n_new = n_new;

@@ -50,7 +50,8 @@ class HostStream:
 
     def step(self, radar_frames):
         g = self.gen
-        points = np.concatenate([np.asarray(f, dtype=float).reshape(4, -1) for f in radar_frames], 1)
+        points = np.concatenate([np.asarray(f, dtype=float).reshape(4, -1) for f in radar_frames], 1) \
+            if len(radar_frames) else np.zeros((4, 0))
         uv_all, xyzv_all = rp.from_3d_to_2d(points, g.calib_param)
         u_all, v_all = rp.projection_xyr_to_uv([points[0], -points[2], points[1]], g.calib_param)
         keep = rp.fov_velocity_filter(uv_all, xyzv_all, g.max_depth, g.min_velocity, *g.image_size)
@@ -120,14 +121,17 @@ def rel_dev(got, ref):
     return float((np.abs(got - ref) / np.maximum(1.0, np.abs(ref))).max())
 
 
-def kalman_deviation(streams=STREAMS, frames=FRAMES):
-    """The host tracker over the test streams twice - as committed, and with :func:`solve_gain` - and the largest deviation
-    (:func:`rel_dev`) of the Kalman state ``x`` / ``P`` and of the pixel proposals between the two runs."""
+def kalman_runs(streams=STREAMS, frames=FRAMES, radar=None, host=None):
+    """The host tracker over the streams of a scene twice - as committed, and with :func:`solve_gain`.  ``radar(s, f)``: the
+    scene (default :func:`stream_radar`); ``host()``: builds one stream's :class:`HostStream` (default: its defaults).  Returns
+    the records ``[frame][stream]`` of the committed run and the largest deviation (:func:`rel_dev`) of the Kalman state
+    ``x`` / ``P`` and of the pixel proposals between the two runs."""
+    radar, host = radar or stream_radar, host or HostStream
     runs = []
     for solve in (False, True):
         with (solve_gain() if solve else contextlib.nullcontext()):
-            hosts = [HostStream() for _ in range(streams)]
-            runs.append([[hosts[s].step(stream_radar(s, f)) for s in range(streams)] for f in range(frames)])
+            hosts = [host() for _ in range(streams)]
+            runs.append([[hosts[s].step(radar(s, f)) for s in range(streams)] for f in range(frames)])
     worst = 0.0
     for step_a, step_b in zip(*runs):
         for a, b in zip(step_a, step_b):
@@ -135,13 +139,18 @@ def kalman_deviation(streams=STREAMS, frames=FRAMES):
             worst = max(worst, rel_dev(b["proposals"], a["proposals"]))
             for ta, tb in zip(a["state"], b["state"]):
                 worst = max(worst, rel_dev(tb["x"], ta["x"]), rel_dev(tb["P"], ta["P"]))
-    return worst
+    return runs[0], worst
 
 
-def kalman_bar():
+def kalman_deviation(streams=STREAMS, frames=FRAMES, radar=None, host=None):
+    """The deviation of :func:`kalman_runs` (by default: over the streams of tests/test_gpu_multistream.py)."""
+    return kalman_runs(streams, frames, radar, host)[1]
+
+
+def kalman_bar(streams=STREAMS, frames=FRAMES, radar=None, host=None):
     """16 x the measured deviation: headroom for fused multiply-add contraction in the host BLAS and another elimination
     order on the device."""
-    return 16.0 * kalman_deviation()
+    return 16.0 * kalman_deviation(streams, frames, radar, host)
 
 
 def rows8(rows7, frame_hw, img_size=416):
