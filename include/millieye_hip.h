@@ -336,6 +336,23 @@ int me_roi_heads_f32(const me_heads_desc* d, void* stream);
  * valid; count [1] int32.  One launch: every kept row computes its own rank against all keys (broadcast LDS reads). */
 int me_compact_sort_rows_f32(const float* rows, const uint8_t* keep, const float* key, int32_t cap, int32_t cols, float* out,
                              int32_t* count, void* stream);
+/* Per-frame modes: one Network.forward for a batch in which some frames take fusion (mode 0) and the others the detector alone
+ * (mode 1).  replaces: the two Network.forward calls of demo.MultiStreamFuser on a mixed step (run_mp.py:204-212 picks one mode
+ *   per frame; the reference has no batched form), i.e. torch.cat of a mode-0 call's rows and a mode-1 call's rows
+ *   (my_models.py:475-476), each filtered to its own frames.
+ * me_roi_heads_modes_f32 - me_roi_heads_f32 (inference) with frame_mode [d->n] int32 on the device: 0 = fusion, anything else =
+ *   camera only.  Needs d->pool_scratch (the pooling launch + the matrix-pipe heads) and refuses the training saves
+ *   (ME_E_BADARG).  Per RoI k, by the mode of the frame in its column 0 (trusted like me_roi_heads_f32 trusts it: an integer
+ *   in [0, n)):  mode 0: everything me_roi_heads_f32 writes for k, bit for bit, its pool_scratch row included;
+ *   camera only, image proposal: out_rows[k] = img_boxes[k][0:8] and keep[k] = 2, nothing else is written for k;
+ *   camera only, radar RoI: keep[k] = 0, nothing else is written.  Slots behind the last RoI: keep = 0.
+ * me_compact_sort_rows_modes_f32 - me_compact_sort_rows_f32 with pass-through rows: the rows with keep == 2 follow the ranked
+ *   rows (every other non-zero keep; order as above) in ascending row order.  counts [2] int32 = (ranked, passed through);
+ *   out's first counts[0] + counts[1] rows are valid.  One launch; with keep in {0, 1} out and counts[0] are those of
+ *   me_compact_sort_rows_f32. */
+int me_roi_heads_modes_f32(const me_heads_desc* d, const int32_t* frame_mode, void* stream);
+int me_compact_sort_rows_modes_f32(const float* rows, const uint8_t* keep, const float* key, int32_t cap, int32_t cols,
+                                   float* out, int32_t* counts, void* stream);
 
 /* Stage 2 (module2_mixed/my_models.py:299-364) heads for every box of every class: PS-RoIAlign (7x7, 490 -> 10 maps) on
  * img_map, refinement_head((490,256,class_num+1)) (net0 LeakyReLU, net1 -> regress [cap,4], net2 sigmoid -> refine
@@ -671,7 +688,10 @@ int me_radar_heatmap_f32(const double* points, const int32_t* offsets, const int
  *   offsets) of me_radar_heatmap_f32; totals [2] = (boxes, points).
  *   A stream that exceeds a capacity gets status ME_RADAR_E_* , all-zero counts and an UNCHANGED state; the call returns 0.
  * me_frame_means_f32: means[f] = mean of the elems_per_frame floats of frame f (double accumulation, fixed order) - the
- *   img.mean() of the demos' auto mode (run_mp.py:204-212) for a whole batch. */
+ *   img.mean() of the demos' auto mode (run_mp.py:204-212) for a whole batch.
+ * me_frame_modes_f32: the same means (same bits) and the auto mode's decision with them, replaces: mode_selection's
+ *   `img.mean() < 0.08` (run_mp.py:204-212) per frame: modes[f] = ((double)means[f] < threshold) ? 0 : 1 - 0 fusion, 1 camera
+ *   only; the comparison is in double, like Python's float(mean) < threshold. */
 #define ME_RADAR_MAX_POINTS 256
 #define ME_RADAR_MAX_CLUSTERS 32
 #define ME_RADAR_MAX_TRACKS 32
@@ -716,6 +736,8 @@ int64_t me_radar_tracker_state_bytes(int32_t streams);
 int me_radar_tracker_reset(void* state, int32_t streams, int32_t which, void* stream);
 int me_radar_proposals_f64(const me_radar_desc* d, void* stream);
 int me_frame_means_f32(const float* imgs, int32_t n, int64_t elems_per_frame, float* means, void* stream);
+int me_frame_modes_f32(const float* imgs, int32_t n, int64_t elems_per_frame, double threshold, float* means, int32_t* modes,
+                       void* stream);
 
 /* ---- evaluation tail -----------------------------------------------------------------
  * get_batch_statistics (module3_our_dataset/utils/utils.py:185-236) for one batch, on the output rows of

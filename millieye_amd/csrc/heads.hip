@@ -15,6 +15,9 @@
 //   inference, stage 3 (Network.forward -> me_roi_heads_f32 with me_heads_desc.pool_scratch set):
 //       roi_pool10_kernel (a thread per bin, ten channels each)  +  roi_heads_mfma_kernel (32 RoIs per workgroup, net0 on the fp32
 //       matrix pipe)  +  compact_sort_kernel.                                                        <- the product path
+//   inference with a mode per frame (Network.forward(frame_modes=) -> me_roi_heads_modes_f32): the same two launches with a
+//       frame_mode vector - roi_pool10_kernel skips the RoIs of camera-only frames, roi_heads_mfma_kernel<true> masks their rows -
+//       + compact_sort_kernel<true> (ranked rows, then the passed-through proposals).                  <- product, opt-in
 //   training, stage 3 (train_path.py: save_* pointers set): roi_heads_kernel (8 RoIs per workgroup, VALU chains; writes the saved
 //       activations the backward needs) and the *_bwd kernels.                                         <- product for training
 //   cross-checks only: roi_heads_kernel as the single fused launch of inference (pool_scratch == NULL; Network._fused_heads,
@@ -285,7 +288,9 @@ __device__ __forceinline__ void tail_one(const me_heads_desc& d, const float* sm
 // (bin, channel) with the channel fastest - the ten lanes of a bin share their sample points, so on the radar map (NHWC, 10
 // channels) and on a bin-major image map (me_heads_desc.img_bin_major) a sample corner is ONE 40-byte read per ten lanes instead
 // of ten cache lines; the values go through LDS to their slots f = c * 49 + bin and leave as contiguous rows.
-__global__ __launch_bounds__(256) void roi_pool_kernel(me_heads_desc d) {
+// frame_mode (me_roi_heads_modes_f32; nullptr = every frame refines): the RoIs of a camera-only frame are not pooled - their row of
+// pool_scratch is left as it is and the workgroup leaves before it touches the maps.
+__global__ __launch_bounds__(256) void roi_pool_kernel(me_heads_desc d, const int* __restrict__ frame_mode) {
   __shared__ float s_box[5];
   __shared__ float s_out[2 * FEAT];
   const int t = threadIdx.x;
@@ -294,6 +299,7 @@ __global__ __launch_bounds__(256) void roi_pool_kernel(me_heads_desc d) {
   if (k >= n_img + d.n_radar) return;
   if (t < 5) s_box[t] = (k < n_img) ? d.img_boxes[(long long)k * d.box_cols + t] : d.radar_boxes[(long long)(k - n_img) * 5 + t];
   __syncthreads();
+  if (frame_mode && frame_mode[(int)s_box[0]] != 0) return;  // (uniform: every thread reads the same word)
   for (int i = t; i < 2 * FEAT; i += 256) {
     const int part = i >= FEAT ? 1 : 0, q = i - part * FEAT;
     const int bin = q / C_OUT, c = q - bin * C_OUT;
@@ -407,7 +413,7 @@ __device__ void roi_sample10(const float* map, long long pitch, int height, int 
 }
 
 // one RoI per workgroup of 128 threads: thread t < 49 = image bin t, 49 <= t < 98 = radar bin t - 49
-__global__ __launch_bounds__(128) void roi_pool10_kernel(me_heads_desc d) {
+__global__ __launch_bounds__(128) void roi_pool10_kernel(me_heads_desc d, const int* __restrict__ frame_mode) {
   __shared__ float s_box[5];
   __shared__ float s_out[2 * FEAT];
   const int t = threadIdx.x;
@@ -416,6 +422,7 @@ __global__ __launch_bounds__(128) void roi_pool10_kernel(me_heads_desc d) {
   if (k >= n_img + d.n_radar) return;
   if (t < 5) s_box[t] = (k < n_img) ? d.img_boxes[(long long)k * d.box_cols + t] : d.radar_boxes[(long long)(k - n_img) * 5 + t];
   __syncthreads();
+  if (frame_mode && frame_mode[(int)s_box[0]] != 0) return;  // (see roi_pool_kernel)
   if (t < 2 * PP) {
     const int part = t >= PP ? 1 : 0, bin = t - part * PP;
     const int ph = bin / P, pw = bin - ph * P;
@@ -614,7 +621,15 @@ constexpr int HP = HID + 4;    // 260
 constexpr int kHeadsMfmaFloats = RM * FPI + RM * HP + RM * 16 + RM * 5 + 256 + 6 * HID + C_OUT * FPI;
 constexpr size_t kHeadsMfmaLds = (size_t)kHeadsMfmaFloats * sizeof(float);
 
-__global__ __launch_bounds__(256) void roi_heads_mfma_kernel(me_heads_desc d, int stop) {
+//
+// MODES (me_roi_heads_modes_f32): frame_mode [d.n] on the device, 0 = the frame's RoIs are refined as above, anything else = camera
+// only: an image proposal of such a frame passes through (out_rows = its img_boxes row, keep = 2), a radar RoI is dropped
+// (keep = 0), and nothing else is written for either.  Their rows of the 32-RoI tile are masked to zero like the rows behind the
+// last RoI - the rows of an MFMA product are independent, so the live rows keep their bits - and a workgroup without a live row
+// leaves before it reads a feature or a weight.  A template, not a run-time nullptr test: the product instantiation
+// (MODES = false) keeps the code it had.
+template <bool MODES>
+__global__ __launch_bounds__(256) void roi_heads_mfma_kernel(me_heads_desc d, int stop, const int* __restrict__ frame_mode) {
   extern __shared__ __attribute__((aligned(16))) float heads_lds[];
   float* s_f = heads_lds;            // [RM][FPI] image features, then radar features
   float* s_hid = s_f + RM * FPI;     // [RM][HP]
@@ -630,6 +645,36 @@ __global__ __launch_bounds__(256) void roi_heads_mfma_kernel(me_heads_desc d, in
   if (t < RM && k0 + t >= total && k0 + t < d.n_img_cap + d.n_radar) d.keep[k0 + t] = 0;  // (see roi_heads_kernel)
   if (k0 >= total) return;
   const int nr = (total - k0 < RM) ? total - k0 : RM;
+  unsigned live = 0xffffffffu;  // bit r: row r of the tile is refined (MODES: a wave-uniform mask; else r < nr decides alone)
+  if constexpr (MODES) {
+    // (the mask's word is borrowed from s_small, which phase C writes two barriers later: a static __shared__ word would sit in
+    //  front of the dynamic region and take its base off 16 bytes)
+    unsigned& s_live = *reinterpret_cast<unsigned*>(s_small);
+    if (wv == 0) {  // lane r < nr looks up the mode of its RoI's frame and writes what a skipped RoI gets
+      bool on = false;
+      if (lane < nr) {
+        const int k = k0 + lane;
+        const float* box = (k < n_img) ? d.img_boxes + (long long)k * d.box_cols : d.radar_boxes + (long long)(k - n_img) * 5;
+        on = frame_mode[(int)box[0]] == 0;
+        if (!on) {
+          if (k < n_img) {
+            float* o = d.out_rows + 8ll * k;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) o[c] = box[c];
+            d.keep[k] = 2;
+          } else {
+            d.keep[k] = 0;
+          }
+        }
+      }
+      const unsigned long long m = __ballot(on);
+      if (lane == 0) s_live = (unsigned)m;
+    }
+    __syncthreads();
+    live = s_live;
+    if (live == 0u) return;
+  }
+  auto row_on = [&](int r) { return MODES ? ((live >> r) & 1u) != 0u : r < nr; };
   if (t < RM * 5) {
     const int r = t / 5, c = t % 5;
     float v = 0.f;
@@ -648,7 +693,7 @@ __global__ __launch_bounds__(256) void roi_heads_mfma_kernel(me_heads_desc d, in
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int f = t + 256 * h;
-        st[u][h] = (u < nr && f < FEAT) ? src[(long long)u * 2 * FEAT + f] : 0.f;
+        st[u][h] = (row_on(u) && f < FEAT) ? src[(long long)u * 2 * FEAT + f] : 0.f;
       }
   };
   auto feats_commit = [&](float (*st)[2]) {
@@ -759,7 +804,7 @@ __global__ __launch_bounds__(256) void roi_heads_mfma_kernel(me_heads_desc d, in
   // and, for (t & 7) < 2, 8 + (t & 7).
   {
     const int r = t >> 3, jj = t & 7;
-    if (r < nr && jj < 6) {
+    if (row_on(r) && jj < 6) {
       const float4* wrow = reinterpret_cast<const float4*>(s_w12 + jj * HID);
       const float4* hrow = reinterpret_cast<const float4*>(s_hid + r * HP);
       float acc = 0.f;
@@ -772,7 +817,7 @@ __global__ __launch_bounds__(256) void roi_heads_mfma_kernel(me_heads_desc d, in
     }
     __syncthreads();  // the radar rows are in LDS
     if (stop == 3) return;
-    if (r < nr) {
+    if (row_on(r)) {
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
         const int o = jj + 8 * half;  // radar conv output
@@ -802,7 +847,7 @@ __global__ __launch_bounds__(256) void roi_heads_mfma_kernel(me_heads_desc d, in
     return;   // (the tail runs separately, once the RoI-wise BatchNorm statistics are known: me_heads_tail_f32)
   }
   // phase D: one thread per RoI - scalar tail (its weights from LDS)
-  if (t < nr)
+  if (MODES ? (t < RM && row_on(t)) : t < nr)
     tail_one(d, s_small + t * 16, s_roi + t * 5, k0 + t, n_img,
              TailW{s_ens, s_ens + 64, s_ens + 96, s_ens + 224, s_ens + 234, s_ens + 244, s_ens + 254});
 }
@@ -1059,20 +1104,31 @@ constexpr int kSortRows = 16;  // rows per workgroup; 16 lanes share one row and
 // One workgroup = 16 rows x 16 key partitions (partition p takes the keys j with j % 16 == p: the 16 lanes of a row read 16
 // consecutive LDS words, the 4 rows of a wave broadcast).  A 6464-row batch-32 step is 404 workgroups / 1616 waves instead
 // of one thread per row looping over every key (that version was VALU-bound on 26 CUs: 208 us; this one 15 us).
+//
+// MODES (me_compact_sort_rows_modes_f32): a row with keep == 2 is passed through, not ranked: the passed-through rows follow the
+// ranked ones in ascending row order, so the rank of one is the number of ranked rows plus the number of passed-through rows in
+// front of it - two more counts in the same walk over the tiles (a byte per row beside the key); count = (ranked, passed through).
+template <bool MODES>
 __global__ __launch_bounds__(256) void compact_sort_kernel(const float* __restrict__ rows, const unsigned char* __restrict__ keep,
                                                            const float* __restrict__ key, int cap, int cols,
                                                            float* __restrict__ out, int* __restrict__ count) {
   __shared__ float sk[kSortTile];
+  __shared__ unsigned char sp[MODES ? kSortTile : 1];  // 1: the row is passed through
   const int part = threadIdx.x & 15;
   const int i = blockIdx.x * kSortRows + (threadIdx.x >> 4);
-  const bool mine = i < cap && keep[i] != 0;
+  const unsigned char mode_i = i < cap ? keep[i] : 0;
+  const bool pass = MODES && mode_i == 2;
+  const bool mine = mode_i != 0 && !pass;
   const float ki = mine ? key[i] : 0.f;
-  int rank = 0, total = 0;
+  int rank = 0, total = 0, pass_before = 0, pass_total = 0;
   for (int t0 = 0; t0 < cap; t0 += kSortTile) {
     __syncthreads();
     for (int j = threadIdx.x; j < kSortTile; j += 256) {
       const int g = t0 + j;
-      sk[j] = (g < cap && keep[g] != 0) ? key[g] : __builtin_nanf("");  // dropped rows never compare greater / equal
+      const unsigned char kg = g < cap ? keep[g] : 0;
+      const bool passed = MODES && kg == 2;
+      sk[j] = (kg != 0 && !passed) ? key[g] : __builtin_nanf("");  // dropped rows never compare greater / equal
+      if (MODES) sp[j] = passed ? 1 : 0;
     }
     __syncthreads();
     const int lim = (cap - t0 < kSortTile ? cap - t0 : kSortTile);
@@ -1080,17 +1136,30 @@ __global__ __launch_bounds__(256) void compact_sort_kernel(const float* __restri
       const float kj = sk[k];
       rank += (kj > ki) || (kj == ki && t0 + k < i);
       total += kj == kj;
+      if (MODES) {
+        const int p = sp[k];
+        pass_total += p;
+        pass_before += (t0 + k < i) ? p : 0;
+      }
     }
   }
 #pragma unroll
   for (int o = 8; o >= 1; o >>= 1) {
     rank += __shfl_xor(rank, o, 16);
     total += __shfl_xor(total, o, 16);
+    if (MODES) {
+      pass_before += __shfl_xor(pass_before, o, 16);
+      pass_total += __shfl_xor(pass_total, o, 16);
+    }
   }
-  if (mine)
+  if (pass) rank = total + pass_before;
+  if (mine || pass)
     for (int c = part; c < cols; c += 16) out[(long long)rank * cols + c] = rows[(long long)i * cols + c];
   // (system scope: the count word may be pinned host memory that the caller polls)
-  if (i == 0 && part == 0) __hip_atomic_store(count, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (i == 0 && part == 0) {
+    __hip_atomic_store(count, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (MODES) __hip_atomic_store(count + 1, pass_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
 }
 
 }  // namespace
@@ -1135,8 +1204,8 @@ int me_m2_heads_f32(const float* img_map, int64_t img_pitch, int32_t n, int32_t 
   return me::check_launch("m2_heads_kernel");
 }
 
-int me_roi_heads_f32(const me_heads_desc* d, void* stream_) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+// me_roi_heads_f32 (frame_mode == nullptr) and me_roi_heads_modes_f32
+static int launch_roi_heads(const me_heads_desc* d, const int32_t* frame_mode, hipStream_t stream) {
   ME_REQUIRE(d, ME_E_NULLPTR, "me_roi_heads_f32: null descriptor");
   ME_REQUIRE(d->img_map && d->radar_map && d->img_boxes && d->n_img, ME_E_NULLPTR, "me_roi_heads_f32: null input");
   ME_REQUIRE(d->n_radar == 0 || d->radar_boxes, ME_E_NULLPTR, "me_roi_heads_f32: null radar_boxes");
@@ -1158,18 +1227,26 @@ int me_roi_heads_f32(const me_heads_desc* d, void* stream_) {
   if (cap == 0) return 0;
   if (d->pool_scratch) {
     static const int pool10 = getenv("MILLIEYE_POOL10") ? atoi(getenv("MILLIEYE_POOL10")) : 1;
-    if (pool10) hipLaunchKernelGGL(roi_pool10_kernel, dim3(cap), dim3(128), 0, stream, *d);
-    else hipLaunchKernelGGL(roi_pool_kernel, dim3(cap), dim3(256), 0, stream, *d);
+    if (pool10) hipLaunchKernelGGL(roi_pool10_kernel, dim3(cap), dim3(128), 0, stream, *d, frame_mode);
+    else hipLaunchKernelGGL(roi_pool_kernel, dim3(cap), dim3(256), 0, stream, *d, frame_mode);
     const int rc = me::check_launch("roi_pool_kernel");
     if (rc) return rc;
   }
   static const int mfma_env = getenv("MILLIEYE_HEADS_MFMA") ? atoi(getenv("MILLIEYE_HEADS_MFMA")) : 1;
+  if (frame_mode) {  // per-frame modes: the matrix-pipe heads are the one kernel that takes them
+    static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(roi_heads_mfma_kernel<true>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHeadsMfmaLds);
+    ME_HIP(attr);
+    hipLaunchKernelGGL(roi_heads_mfma_kernel<true>, dim3((cap + RM - 1) / RM), dim3(256), kHeadsMfmaLds, stream, *d, 0, frame_mode);
+    return me::check_launch("roi_heads_mfma_kernel<modes>");
+  }
   if (mfma_env && d->pool_scratch) {  // pooled rows (inference, and training since round 6): net0 on the matrix pipe, 32 RoIs per workgroup
-    static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(roi_heads_mfma_kernel),
+    static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(roi_heads_mfma_kernel<false>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHeadsMfmaLds);
     ME_HIP(attr);
     static const int stop = getenv("MILLIEYE_HEADS_STOP") ? atoi(getenv("MILLIEYE_HEADS_STOP")) : 0;  // profiling only
-    hipLaunchKernelGGL(roi_heads_mfma_kernel, dim3((cap + RM - 1) / RM), dim3(256), kHeadsMfmaLds, stream, *d, stop);
+    hipLaunchKernelGGL(roi_heads_mfma_kernel<false>, dim3((cap + RM - 1) / RM), dim3(256), kHeadsMfmaLds, stream, *d, stop,
+                       (const int*)nullptr);
     return me::check_launch("roi_heads_mfma_kernel");
   }
   // few workgroups (batch <= 16: at most two per CU): deep weight prefetch, 189 VGPRs; more: the four-row loop keeps four waves per SIMD
@@ -1178,6 +1255,18 @@ int me_roi_heads_f32(const me_heads_desc* d, void* stream_) {
   if (kc_env ? kc_env == 32 : wgs <= 512) hipLaunchKernelGGL(roi_heads_kernel<32>, dim3(wgs), dim3(256), 0, stream, *d);
   else hipLaunchKernelGGL(roi_heads_kernel<4>, dim3(wgs), dim3(256), 0, stream, *d);
   return me::check_launch("roi_heads_kernel");
+}
+
+int me_roi_heads_f32(const me_heads_desc* d, void* stream) {
+  return launch_roi_heads(d, nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
+int me_roi_heads_modes_f32(const me_heads_desc* d, const int32_t* frame_mode, void* stream) {
+  ME_REQUIRE(d && frame_mode, ME_E_NULLPTR, "me_roi_heads_modes_f32: null descriptor / frame_mode");
+  ME_REQUIRE(d->pool_scratch, ME_E_BADARG, "me_roi_heads_modes_f32: needs pool_scratch (the pooling launch + the matrix-pipe heads)");
+  ME_REQUIRE(!(d->save_small || d->save_feat_img || d->save_feat_rad || d->save_hidden), ME_E_BADARG,
+             "me_roi_heads_modes_f32: inference only (the training saves must be NULL)");
+  return launch_roi_heads(d, frame_mode, reinterpret_cast<hipStream_t>(stream));
 }
 
 static int launch_roi(const float* map, int64_t pitch, int32_t n, int32_t h, int32_t w, int32_t c, const float* rois,
@@ -1271,9 +1360,23 @@ int me_compact_sort_rows_f32(const float* rows, const uint8_t* keep, const float
     return 0;
   }
   ME_REQUIRE(rows && keep && key && out, ME_E_NULLPTR, "me_compact_sort_rows_f32: null pointer");
-  hipLaunchKernelGGL(compact_sort_kernel, dim3((unsigned)((cap + kSortRows - 1) / kSortRows)), dim3(256), 0,
+  hipLaunchKernelGGL(compact_sort_kernel<false>, dim3((unsigned)((cap + kSortRows - 1) / kSortRows)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), rows, keep, key, cap, cols, out, count);
   return me::check_launch("compact_sort_kernel");
+}
+
+int me_compact_sort_rows_modes_f32(const float* rows, const uint8_t* keep, const float* key, int32_t cap, int32_t cols,
+                                   float* out, int32_t* counts, void* stream) {
+  ME_REQUIRE(counts != nullptr, ME_E_NULLPTR, "me_compact_sort_rows_modes_f32: null counts");
+  ME_REQUIRE(cap >= 0 && cols > 0, ME_E_BADARG, "me_compact_sort_rows_modes_f32: bad dimensions");
+  if (cap == 0) {
+    ME_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(int32_t), reinterpret_cast<hipStream_t>(stream)));
+    return 0;
+  }
+  ME_REQUIRE(rows && keep && key && out, ME_E_NULLPTR, "me_compact_sort_rows_modes_f32: null pointer");
+  hipLaunchKernelGGL(compact_sort_kernel<true>, dim3((unsigned)((cap + kSortRows - 1) / kSortRows)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), rows, keep, key, cap, cols, out, counts);
+  return me::check_launch("compact_sort_kernel<modes>");
 }
 
 }  // extern "C"

@@ -667,8 +667,11 @@ __global__ __launch_bounds__(THREADS) void radar_pack_kernel(const int* __restri
 
 // ---- per-frame means ---------------------------------------------------------------------------------------------------------
 constexpr int MEAN_THREADS = 1024;
+// modes (me_frame_modes_f32; nullptr = means only): the auto mode's rule on the mean just stored, compared in double like the
+// host's ``float(mean) < dark_threshold``: 0 = fusion (dark frame), 1 = camera only.
 __global__ __launch_bounds__(MEAN_THREADS) void frame_means_kernel(const float* __restrict__ imgs, long long elems,
-                                                                   float* __restrict__ means) {
+                                                                   float* __restrict__ means, double threshold,
+                                                                   int* __restrict__ modes) {
   __shared__ double s_part[MEAN_THREADS];
   const float* x = imgs + (size_t)blockIdx.x * elems;
   double acc = 0.0;
@@ -687,7 +690,11 @@ __global__ __launch_bounds__(MEAN_THREADS) void frame_means_kernel(const float* 
     if (threadIdx.x < step) s_part[threadIdx.x] += s_part[threadIdx.x + step];
     __syncthreads();
   }
-  if (threadIdx.x == 0) means[blockIdx.x] = (float)(s_part[0] / (double)elems);
+  if (threadIdx.x == 0) {
+    const float mean = (float)(s_part[0] / (double)elems);
+    means[blockIdx.x] = mean;
+    if (modes) modes[blockIdx.x] = ((double)mean < threshold) ? 0 : 1;
+  }
 }
 
 }  // namespace
@@ -747,7 +754,17 @@ int me_frame_means_f32(const float* imgs, int32_t n, int64_t elems_per_frame, fl
   ME_REQUIRE(imgs && means, ME_E_NULLPTR, "me_frame_means_f32: null pointer");
   ME_REQUIRE(n > 0 && elems_per_frame > 0, ME_E_BADARG, "me_frame_means_f32: bad n / elems_per_frame");
   hipLaunchKernelGGL(frame_means_kernel, dim3(n), dim3(MEAN_THREADS), 0, (hipStream_t)stream, imgs, (long long)elems_per_frame,
-                     means);
+                     means, 0.0, (int*)nullptr);
+  return me::check_launch("frame_means_kernel");
+}
+
+int me_frame_modes_f32(const float* imgs, int32_t n, int64_t elems_per_frame, double threshold, float* means, int32_t* modes,
+                       void* stream) {
+  if (n == 0) return 0;
+  ME_REQUIRE(imgs && means && modes, ME_E_NULLPTR, "me_frame_modes_f32: null pointer");
+  ME_REQUIRE(n > 0 && elems_per_frame > 0, ME_E_BADARG, "me_frame_modes_f32: bad n / elems_per_frame");
+  hipLaunchKernelGGL(frame_means_kernel, dim3(n), dim3(MEAN_THREADS), 0, (hipStream_t)stream, imgs, (long long)elems_per_frame,
+                     means, threshold, modes);
   return me::check_launch("frame_means_kernel");
 }
 

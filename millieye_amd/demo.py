@@ -140,6 +140,14 @@ class MultiStreamFuser:
     on an MI355X the tail alone takes 0.05 - 0.17 ms on the device against 0.15 - 2.5 ms on the host (S = 1 .. 32) and the whole
     step is 10 - 42 % shorter in every row of ``profiles/multistream_latency.txt``.
 
+    ``split="forwards"`` (default): a step whose streams pick different modes reads the S means back, gathers the fusion and the
+    camera-only sub-batch and runs ``Network.forward`` on each - the detector runs at batch ``a`` and ``S - a`` for ``a`` dark
+    streams, a plan per size.  ``split="frame_modes"``: ``hip.frame_modes`` decides on the device (fixed modes 0 / 1: a constant
+    vector; a fixed mode 2 keeps the scalar call) and ONE ``Network.forward(..., frame_modes=)`` takes all S streams at the
+    fixed batch S - no read-back in front of the network, no gather, one detector plan whatever the light does; every stream's
+    rows are ``torch.equal`` to what the whole batch gives at that stream's mode.  The modes reach ``info["mode"]`` in one small
+    copy behind the tail.  Measured against ``"forwards"`` in ``profiles/multistream_frame_modes.txt``.
+
     The device tail lists every stream in a ``[streams][m]`` workspace (``m`` = the rows of the step, the one bound of a
     stream's rows the host holds without a read-back): it raises :class:`hip.MeError` for more than 32768 rows in a step, where
     the host tail only needs every stream's own rows to stay under that, and its workspace grows as ``streams * m``.
@@ -156,11 +164,14 @@ class MultiStreamFuser:
     raise at that first use; touch ``fuser.generator`` after construction to have them raise early."""
 
     def __init__(self, model, calib_params, streams, model_mode=3, img_size=416, nms_iou=0.3, dark_threshold=0.08,
-                 tail="device", **generator_kwargs):
+                 tail="device", split="forwards", **generator_kwargs):
         self.model, self.model_mode, self.img_size, self.streams = model, model_mode, img_size, int(streams)
         self.nms_iou, self.dark_threshold = nms_iou, dark_threshold
         if tail not in ("device", "host"):
             raise hip.MeError(f"MultiStreamFuser: tail must be 'device' or 'host' (got {tail!r})")
+        if split not in ("forwards", "frame_modes"):
+            raise hip.MeError(f"MultiStreamFuser: split must be 'forwards' or 'frame_modes' (got {split!r})")
+        self.split = split
         if self.streams <= 0:
             raise hip.MeError(f"MultiStreamFuser: streams must be positive (got {streams})")
         self.tail = tail
@@ -168,6 +179,7 @@ class MultiStreamFuser:
         self._device = getattr(model, "device", None)
         self._generator = None
         self._scalars = (None, None)   # (frame sizes, their rescale scalars on the device)
+        self._fixed_modes = {}         # split="frame_modes" with a fixed mode 0 / 1: the constant vector on the device
 
     @property
     def device(self):
@@ -199,6 +211,22 @@ class MultiStreamFuser:
         means = hip.frame_means(img).cpu()   # one launch, one copy of S floats
         return [0 if float(m) < self.dark_threshold else 1 for m in means]
 
+    def _infer_frame_modes(self, img, radar_map, step, hws):
+        """``split="frame_modes"``: the modes are decided on the device (auto) or are a constant vector (fixed 0 / 1), one
+        ``Network.forward(..., frame_modes=)`` takes all S streams - no sub-batches, no read-back in front of the network - and
+        the modes come to the host in one small copy behind the tail, for ``info["mode"]`` alone."""
+        n = self.streams
+        if self.model_mode == 3:
+            modes_dev = hip.frame_modes(img, self.dark_threshold)[0]
+        else:
+            modes_dev = self._fixed_modes.get(self.model_mode)
+            if modes_dev is None:
+                modes_dev = self._fixed_modes[self.model_mode] = torch.full((n,), int(self.model_mode), dtype=torch.int32).to(self.device)
+        with torch.no_grad():
+            rows = self.model(img, radar_map, step.radar_box, frame_modes=modes_dev)
+            per_stream = self._tail(rows, hws)
+        return per_stream, modes_dev.cpu().tolist()
+
     def infer(self, payload):
         """Device half: radar chain, input kernels, mode selection, ``Network.forward`` per mode, second NMS, rescale."""
         dev, n = self.device, self.streams
@@ -207,6 +235,9 @@ class MultiStreamFuser:
         step = self.generator.gen(payload["radar_frames"], hws)
         radar_map = self.generator.heatmaps(32)   # the raw 32 x 32 maps, like FrameFuser (quirk q15)
         counts = step.host_counts
+        if self.split == "frame_modes" and self.model_mode in (0, 1, 3):   # (a fixed mode 2 has no per-frame form: scalar call)
+            per_stream, modes = self._infer_frame_modes(img, radar_map, step, hws)
+            return self._results(per_stream, modes, counts)
         modes = self._modes(img)
         box_start = np.concatenate([[0], np.cumsum(counts[:, 4])])
         outs = []
@@ -227,6 +258,10 @@ class MultiStreamFuser:
                 outs.append(rows)
             rows = torch.cat(outs, 0) if len(outs) > 1 else outs[0]
             per_stream = self._tail(rows, hws)
+        return self._results(per_stream, modes, counts)
+
+    def _results(self, per_stream, modes, counts):
+        n = self.streams
         proposals = self.generator._proposals.cpu().numpy()
         result = []
         for s in range(n):

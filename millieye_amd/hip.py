@@ -202,11 +202,14 @@ SIGNATURES = {
     "me_radar_tracker_reset": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "me_radar_proposals_f64": (C.c_int, [C.POINTER(RadarDesc), C.c_void_p]),
     "me_frame_means_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+    "me_frame_modes_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "me_conv2d_f32": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
     "me_conv2d_flops": (C.c_int64, [C.POINTER(ConvDesc)]),
     "me_conv2d_workspace_bytes": (C.c_int64, [C.POINTER(ConvDesc)]),
     "me_compact_sort_rows_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
+    "me_compact_sort_rows_modes_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
     "me_conv2d_h16": (C.c_int, [C.POINTER(Conv16Desc), C.c_void_p]),
     "me_bneck_h16": (C.c_int, [C.POINTER(Bneck16Desc), C.c_void_p]),
     "me_bneck_h16_supported": (C.c_int, [C.POINTER(Bneck16Desc)]),
@@ -239,6 +242,7 @@ SIGNATURES = {
     "me_gather_class_boxes_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "me_roi_heads_f32": (C.c_int, [C.POINTER(HeadsDesc), C.c_void_p]),
+    "me_roi_heads_modes_f32": (C.c_int, [C.POINTER(HeadsDesc), C.c_void_p, C.c_void_p]),
     "me_linear_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                 C.c_void_p, C.c_int64, C.c_void_p]),
     "me_mask_scale_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p, C.c_void_p]),
@@ -1065,3 +1069,20 @@ def frame_means(imgs):
         check(lib().me_frame_means_f32(imgs.data_ptr(), n, imgs.numel() // n, means.data_ptr(), stream_ptr()),
               "me_frame_means_f32")
     return means
+
+
+def frame_modes(imgs, threshold):
+    """The auto mode's decision for every frame of a contiguous float32 CUDA batch ``[n, ...]`` in one launch
+    (``me_frame_modes_f32``) -> ``(modes, means)``: ``means`` as :func:`frame_means` gives them (same bits), ``modes`` int32
+    ``[n]`` on the device with ``0 if float(mean) < threshold else 1`` (0 fusion, 1 camera only) - nothing comes back to the
+    host; ``Network.forward(..., frame_modes=modes)`` takes the tensor as it is."""
+    _require_cuda_f32(imgs, "imgs")
+    if not imgs.is_contiguous():
+        raise MeError("imgs must be contiguous")
+    n = int(imgs.shape[0])
+    means = torch.empty((n,), device=imgs.device, dtype=torch.float32)
+    modes = torch.empty((n,), device=imgs.device, dtype=torch.int32)
+    if n:
+        check(lib().me_frame_modes_f32(imgs.data_ptr(), n, imgs.numel() // n, float(threshold), means.data_ptr(),
+                                       modes.data_ptr(), stream_ptr()), "me_frame_modes_f32")
+    return modes, means

@@ -509,12 +509,46 @@ class Network(nn.Module):
         self.__dict__["_next_images"] = images_next
 
     # ---------------------------------------------------------------------------------- forward
-    def forward(self, images, maps, radar_boxes_location, model_mode=0, targets=None):
+    def _frame_modes_arg(self, frame_modes, n, dev, model_mode, targets):
+        """``forward``'s ``frame_modes`` -> int32 ``[n]`` on the device (0 fusion, non-zero camera only)."""
+        if targets is not None or isinstance(model_mode, torch.Tensor):
+            raise hip.MeError("Network.forward: frame_modes is an inference argument; it cannot be combined with targets")
+        if model_mode != 0:
+            raise hip.MeError(f"Network.forward: frame_modes replaces model_mode; leave model_mode at 0 (got {model_mode!r})")
+        if any(b.training for b in self._head_bns()):
+            raise hip.MeError("Network.forward: frame_modes needs the head BatchNorms in eval() mode")
+        if isinstance(frame_modes, torch.Tensor) and frame_modes.is_cuda:
+            if frame_modes.dtype != torch.int32 or tuple(frame_modes.shape) != (n,) or frame_modes.device != dev:
+                raise hip.MeError(f"Network.forward: a device frame_modes must be int32 [{n}] on {dev} (got "
+                                  f"{frame_modes.dtype} {tuple(frame_modes.shape)} on {frame_modes.device})")
+            return frame_modes.contiguous()   # used as it is: no read-back, any non-zero value is camera only
+        host = np.asarray(frame_modes.numpy() if isinstance(frame_modes, torch.Tensor) else frame_modes)
+        if host.ndim != 1 or host.shape[0] != n:
+            raise hip.MeError(f"Network.forward: frame_modes needs one mode per frame ({n}), got shape {tuple(host.shape)}")
+        if host.dtype == object or not np.isin(host, (0, 1)).all():
+            raise hip.MeError(f"Network.forward: every frame mode must be 0 (fusion) or 1 (camera only), got {host.tolist()}")
+        return torch.from_numpy(host.astype(np.int32)).to(dev)
+
+    def forward(self, images, maps, radar_boxes_location, model_mode=0, targets=None, frame_modes=None):
         """See the reference docstring (my_models.py:434-450).  Returns ``output [m, 8]`` rows
         ``(image_i, x1, y1, x2, y2, object_conf, class_score, class_pred)`` sorted by confidence.
 
         Compat rule: ``train.py:185`` passes ``targets`` in the ``model_mode`` slot; a
-        tensor there is therefore taken as ``targets`` with mode 0."""
+        tensor there is therefore taken as ``targets`` with mode 0.
+
+        ``frame_modes`` (no reference counterpart; a keyword because a tensor in the ``model_mode`` slot means ``targets``): one
+        mode per frame, 0 = fusion, 1 = camera only - a host sequence / numpy array of 0s and 1s, or an int32 CUDA tensor ``[N]``
+        that is used as it is, without a read-back (any non-zero value is camera only; ``hip.frame_modes`` makes one).  One
+        detector run, one radar CNN and one pair of score maps for all N frames, issued exactly as mode 0 issues them; the RoI
+        heads skip the RoIs of the camera-only frames.  Returns ``torch.cat`` of what a mode-0 call and a mode-1 call return,
+        each filtered to its frames: first the refined rows of the mode-0 frames by confidence, then the unrefined class-
+        ``class_idx`` proposals of the mode-1 frames, image-major in NMS order.  ``radar_boxes_location[:, 1:]`` is ALWAYS
+        scaled in place with ``frame_modes`` - also when every frame is camera only, where a scalar mode-1 call leaves it
+        alone.  ``model_mode`` must stay 0, ``targets`` None and the head BatchNorms in eval() mode (``hip.MeError``)."""
+        if frame_modes is not None:
+            if not images.is_cuda:
+                raise hip.MeError("Network.forward needs CUDA tensors (MI355X); there is no CPU fallback")
+            frame_modes = self._frame_modes_arg(frame_modes, images.shape[0], images.device, model_mode, targets)
         if isinstance(model_mode, torch.Tensor):
             targets, model_mode = model_mode, 0
         if targets is not None:  # training call: (loss, output, metric, radar_attention), reference :545-641
@@ -643,14 +677,28 @@ class Network(nn.Module):
             d.pool_scratch = pooled.data_ptr()
         # (``_fused_heads``: the single-launch VALU kernel with the pooling inside - kept as the cross-check of the two-launch
         # path, tests/test_gpu_network.py)
-        hip.check(lib.me_roi_heads_f32(C.byref(d), hip.stream_ptr()), "me_roi_heads_f32")
+        if frame_modes is not None:
+            if d.pool_scratch is None:
+                raise hip.MeError("Network.forward: frame_modes needs the two-launch heads (_fused_heads is the cross-check path)")
+            hip.check(lib.me_roi_heads_modes_f32(C.byref(d), frame_modes.data_ptr(), hip.stream_ptr()), "me_roi_heads_modes_f32")
+        else:
+            hip.check(lib.me_roi_heads_f32(C.byref(d), hip.stream_ptr()), "me_roi_heads_f32")
         mark("roi_heads")
         tr("heads issued")
         self.refinement_head.count += 1
 
         # ---- keep positives, order by confidence (reference :517-539): one launch, then the one host sync (the row count)
         ordered = torch.empty((cap, 8), **f32)
-        if _COUNT_SPIN:
+        counts = None
+        if frame_modes is not None:   # ranked rows of the mode-0 frames, then the passed-through proposals of the others
+            n_out = self._buf("n_out2", (2,), dev, torch.int32)
+            hip.check(lib.me_compact_sort_rows_modes_f32(rows.data_ptr(), keep.data_ptr(), key.data_ptr(), cap, 8,
+                                                         ordered.data_ptr(), n_out.data_ptr(), hip.stream_ptr()),
+                      "me_compact_sort_rows_modes_f32")
+            tr("compaction issued")
+            counts = tuple(n_out.tolist())   # (the one host sync of the call)
+            n_rows = counts[0] + counts[1]
+        elif _COUNT_SPIN:
             # A/B form of the one host sync of the call (round 5): the kernel stores the count straight into a pinned host word
             # (system-scope store) that the host preset to -1 and polls, instead of ``n_out.item()`` (a 4-byte blocking copy).
             # tools/b1_tail_events.py suggested ~70 us between the end of the compaction kernel and the count on the host; the
@@ -684,4 +732,6 @@ class Network(nn.Module):
         mark("output")
         # (views of pooled scratch: valid only until the next forward of this network on this stream)
         self._last = dict(regress=regress, refine=refine, mask1=mask1, n_img=n_img_dev, img_boxes=img_boxes)
+        if frame_modes is not None:   # (ranked, passed through) and the device modes the launches read
+            self._last.update(counts=counts, frame_modes=frame_modes)
         return output

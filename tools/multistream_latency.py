@@ -14,7 +14,11 @@ the order alternating (host device, device host, ...): "tail
 alone" is ``_tail`` on the network's rows of one recorded step - from the device rows to the per-stream host rows, device
 synchronised - and "step" the whole step with either tail.  The last lines run the S = max row through
 ``pipeline.FusionPipeline`` (two processes, every step inferred) against the in-process fuser: steps/s, the first step
-(spawn, rendezvous) left out."""
+(spawn, rendezvous) left out.
+
+``--split frame_modes`` builds every fuser of those rows with ``MultiStreamFuser(split="frame_modes")`` (one forward with per-frame
+modes); ``--split compare`` prints only the A/B of the two splits (:func:`compare_splits`; profiles/multistream_frame_modes.txt):
+python tools/multistream_latency.py --split compare --streams 8 32 --steps 40 --out profiles/multistream_frame_modes.txt"""
 import argparse
 import os
 import statistics
@@ -75,6 +79,73 @@ def timed(fn, steps, repeats=REPEATS):
     return statistics.median(out)
 
 
+def _demo_net(cfg, dtype):
+    net = Network(Darknet(cfgs.write_cfg(cfg, f"/tmp/ms_lat_{cfg}")), 0.2).eval()
+    synth.fill_network_(net, "demo/" + cfg, cls0_bias=3.0, cls_bias=-4.0)
+    net = net.to(net.device)
+    net.base_detector.compute_dtype = dtype
+    return net
+
+
+def compare_splits(args, say):
+    """``--split compare``: ``MultiStreamFuser(split="frame_modes")`` against ``split="forwards"`` (the yardstick) in one process.
+
+    "mixed" rows: the tests' frames (two sizes, dark and bright interleaved, the dark count fixed), a block of each split in
+    every one of four repeats, the order alternating.  "varying" rows: the number of dark streams changes every step, cycling
+    over nine counts, from cold plan tables (the engines' plans are dropped first; the autotuner's per-layer choices made during
+    the run stay cached, as in a long-running process); the time of every step counts, plan builds included, and the plans built
+    are counted at ``DarknetEngine._build``.  Both fusers of a row see the same frames and radar streams."""
+    say(f"# {torch.cuda.get_device_name(0)}; mixed: {args.steps} steps per block, median of 4 alternating blocks per split, "
+        f"5 warm-up steps; varying: {args.vary_steps} steps per split, every step timed, device synchronised around the run")
+    for cfg in args.cfgs:
+        for dtype in ("f32", "bf16"):
+            net = _demo_net(cfg, dtype)
+            eng = net.base_detector.engine_for(dtype)
+            for n in args.streams:
+                frames = [mh.stream_frame(s) for s in range(n)]
+                dark = sum(s % 3 != 0 for s in range(n))   # (tests.multistream_helpers.stream_frame)
+                radar = [[[radar_points((f + 7 * s) % 45)] for s in range(n)] for f in range(max(args.steps, args.vary_steps))]
+                fusers = {split: MultiStreamFuser(net, RADAR_CALIB, n, model_mode=3, min_hits=2, split=split)
+                          for split in ("forwards", "frame_modes")}
+                for f in range(5):
+                    for fuser in fusers.values():
+                        fuser(frames, radar[f])
+                t_fw, t_fm = timed_ab(lambda f: fusers["forwards"](frames, radar[f]),
+                                      lambda f: fusers["frame_modes"](frames, radar[f]), args.steps)
+                say(f"{cfg:16s} {dtype:4s} S={n:2d} mixed ({dark:2d} dark): forwards {t_fw * 1e3:7.2f} ms/step | frame_modes "
+                    f"{t_fm * 1e3:7.2f} ms/step ({(t_fm / t_fw - 1) * 100:+5.1f} %)")
+            # the dark count changes every step: nine counts spread over 1 .. S - 1
+            n = max(args.streams)
+            if n < 10 or args.vary_steps <= 0:
+                continue
+            counts = sorted({1 + round(i * (n - 2) / 8) for i in range(9)})
+            assert len(counts) == 9
+            bright = [mh.stream_frame(s, dark=False) for s in range(n)]
+            darkf = [mh.stream_frame(s, dark=True) for s in range(n)]
+            built = [0]
+            build = eng._build
+
+            def counting_build(*a, **k):
+                built[0] += 1
+                return build(*a, **k)
+            eng._build = counting_build
+            res = {}
+            for split in ("forwards", "frame_modes", "forwards", "frame_modes"):   # (two runs each: the spread)
+                fuser = MultiStreamFuser(net, RADAR_CALIB, n, model_mode=3, min_hits=2, split=split)
+                eng._plans.clear()
+                built[0] = 0
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for f in range(args.vary_steps):
+                    a = counts[f % 9]
+                    fuser([darkf[s] if s < a else bright[s] for s in range(n)], radar[f])
+                torch.cuda.synchronize()
+                res.setdefault(split, []).append(((time.perf_counter() - t0) / args.vary_steps, built[0]))
+            eng._build = build
+            say(f"{cfg:16s} {dtype:4s} S={n:2d} varying (dark counts {counts}, {args.vary_steps} steps): " + " | ".join(
+                f"{split} " + ", ".join(f"{t * 1e3:7.2f} ms/step with {b} plans built" for t, b in res[split]) for split in res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=100)
@@ -82,6 +153,9 @@ def main():
     ap.add_argument("--cfgs", nargs="*", default=["yolov3-tiny-12", "yolov3"])
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-pipeline", dest="pipeline", action="store_false", help="skip the two-process rows")
+    ap.add_argument("--split", choices=["forwards", "frame_modes", "compare"], default="forwards",
+                    help="MultiStreamFuser(split=...) of every fuser; 'compare': only the A/B of the two splits (compare_splits)")
+    ap.add_argument("--vary-steps", type=int, default=36, help="--split compare: steps of the run with a changing dark count")
     args = ap.parse_args()
     lines = []
 
@@ -90,15 +164,18 @@ def main():
         lines.append(text)
 
     say(f"# python tools/multistream_latency.py {' '.join(sys.argv[1:])}".rstrip())
+    if args.split == "compare":
+        compare_splits(args, say)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return
     say(f"# {torch.cuda.get_device_name(0)}; {args.steps} steps per repeat, median of {REPEATS} repeats, 5 warm-up steps")
     dev = mh.kalman_deviation()
     say(f"# float64 bar of tests/test_gpu_multistream.py: host tracker inv vs solve deviation {dev:.3e}, bar (16 x) {16 * dev:.3e}")
     for cfg in args.cfgs:
         for dtype in ("f32", "bf16"):
-            net = Network(Darknet(cfgs.write_cfg(cfg, f"/tmp/ms_lat_{cfg}")), 0.2).eval()
-            synth.fill_network_(net, "demo/" + cfg, cls0_bias=3.0, cls_bias=-4.0)
-            net = net.to(net.device)
-            net.base_detector.compute_dtype = dtype
+            net = _demo_net(cfg, dtype)
             for n, mixed in [(n, False) for n in args.streams] + [(max(args.streams), True)]:
                 if mixed:   # two frame sizes, dark and bright interleaved: both sub-batches every step
                     frames = [mh.stream_frame(s) for s in range(n)]
@@ -107,8 +184,9 @@ def main():
                 # the seeds wrap every 45 steps: the synthetic reflectors drift out of the filter's depth range after that, and
                 # seed 46 holds a point on the camera plane (tests/multistream_helpers.py)
                 radar = [[[radar_points((f + 7 * s) % 45)] for s in range(n)] for f in range(args.steps)]
-                multi = MultiStreamFuser(net, RADAR_CALIB, n, model_mode=3, min_hits=2)   # the default tail
-                other = MultiStreamFuser(net, RADAR_CALIB, n, model_mode=3, min_hits=2, tail="device" if multi.tail == "host" else "host")
+                multi = MultiStreamFuser(net, RADAR_CALIB, n, model_mode=3, min_hits=2, split=args.split)   # the default tail
+                other = MultiStreamFuser(net, RADAR_CALIB, n, model_mode=3, min_hits=2, split=args.split,
+                                         tail="device" if multi.tail == "host" else "host")
                 multi_host, multi_dev = (multi, other) if multi.tail == "host" else (other, multi)
                 singles = [FrameFuser(net, RADAR_CALIB, model_mode=3, min_hits=2) for _ in range(n)]
                 for f in range(5):   # warm-up: plans, autotuner, allocator
@@ -161,7 +239,7 @@ def main():
                     f"({(t_step_dev / t_step_host - 1) * 100:+5.1f} %)")
                 if n == max(args.streams) and not mixed and args.pipeline:
                     from millieye_amd.pipeline import FusionPipeline
-                    piped = MultiStreamFuser(net, RADAR_CALIB, n, model_mode=3, min_hits=2, tail="device")
+                    piped = MultiStreamFuser(net, RADAR_CALIB, n, model_mode=3, min_hits=2, tail="device", split=args.split)
                     t0, done = None, 0
                     for _results, _info in FusionPipeline(piped, DarkSource(args.steps + 1, n), skip_to_newest=False):
                         if t0 is None:
