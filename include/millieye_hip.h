@@ -661,6 +661,34 @@ int me_image_pad_resize_flip_u8_f32(const uint8_t* src, int32_t h, int32_t w, fl
  * whose bytes do not lie inside src yields an all-zero frame. */
 int me_image_batch_pad_resize_flip_u8_f32(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int32_t n,
                                           float* dst, int32_t size, void* stream);
+/* me_image_batch_formats_u8_f32: me_image_batch_pad_resize_flip_u8_f32 with a pixel format per frame, so that the frames go
+ * to the device the way the camera or the decoder hands them over: the live demo reads BGR from cv2.VideoCapture and converts
+ * on the host before ToTensor (module3_our_dataset/run_mp.py:50,114), USB cameras give YUYV, hardware decoders NV12.
+ * desc [n,5] int64 on the device = (byte offset, h, w, flip, ME_PIXFMT_*) per frame; h, w are the PICTURE's height and width
+ * in pixels whatever the memory layout.  Everything else - one launch, index arithmetic, pad / flip / nearest rules, the IEEE
+ * division by 255, float4 stores for size % 4 == 0, argument checks - is the entry point above.
+ *   ME_PIXFMT_RGB   3hw bytes         [h,w,3], as above.
+ *   ME_PIXFMT_BGR   3hw bytes         [h,w,3], byte 0 is blue; the output planes are still R, G, B.
+ *   ME_PIXFMT_NV12  hw + hw/2 bytes   h, w even.  Y plane [h,w], then the interleaved UV plane [h/2,w]: pixel (y,x) uses
+ *                                     U = uv[y>>1][x & ~1], V = uv[y>>1][(x & ~1) + 1].  Chroma is not interpolated.
+ *   ME_PIXFMT_YUYV  2hw bytes         w even.  Rows of Y0 U Y1 V: pixel (y,x) uses Y = row[2x], U = row[4(x>>1) + 1],
+ *                                     V = row[4(x>>1) + 3].
+ * YUV -> RGB is the integer limited-range BT.601 conversion of cv2.cvtColor with COLOR_YUV2RGB_NV12 / COLOR_YUV2RGB_YUY2
+ * (int32 arithmetic, >> arithmetic):
+ *   y = max(0, Y - 16) * 1220542;  u = U - 128;  v = V - 128
+ *   R = clamp((y + (1 << 19) + 1673527 * v) >> 20, 0, 255)
+ *   G = clamp((y + (1 << 19) - 852492 * v - 409993 * u) >> 20, 0, 255)
+ *   B = clamp((y + (1 << 19) + 2116026 * u) >> 20, 0, 255)
+ * and each of R, G, B then goes through the (float)c / 255.f of the RGB path: a frame in format F gives the bits
+ * me_image_batch_pad_resize_flip_u8_f32 gives on that frame converted to RGB.  A frame whose bytes do not lie inside src,
+ * whose format id is unknown, or whose h / w is odd where its format needs it even (NV12: both, YUYV: w) is not read and
+ * comes out all zero.  No row pitch: frames are dense. */
+#define ME_PIXFMT_RGB 0
+#define ME_PIXFMT_BGR 1
+#define ME_PIXFMT_NV12 2
+#define ME_PIXFMT_YUYV 3
+int me_image_batch_formats_u8_f32(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int32_t n, float* dst,
+                                  int32_t size, void* stream);
 int me_radar_heatmap_f32(const double* points, const int32_t* offsets, const int32_t* sizes, int32_t n,
                          int32_t radar_maps_size, float* out, int32_t map_size, void* stream);
 

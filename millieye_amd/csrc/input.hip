@@ -5,6 +5,9 @@
 //   me_image_batch_pad_resize_flip_u8_f32
 //                               the same for a ragged batch (frames of different sizes packed in one uint8 buffer, one
 //                               descriptor per frame), one launch; with the stage-2 flip (module2_mixed/utils/datasets.py:275-304).
+//   me_image_batch_formats_u8_f32
+//                               the ragged batch with a pixel format per frame (RGB, BGR, NV12, YUYV): the frames a camera
+//                               or a decoder hands over, without the host's conversion to RGB (run_mp.py:50,114).
 //   me_radar_heatmap_f32        plot_radar_heatmap (:59-106: three np.histogram2d in float64, per-bin means, range
 //                               normalisation) + ToTensor().float() (:267) + pad_to_square (:270) +
 //                               F.interpolate(bilinear, align_corners=True) to the map size (:318-321).
@@ -93,6 +96,102 @@ __global__ __launch_bounds__(256) void image_batch_pad_resize_kernel(const unsig
   if ((S & 3) == 0) {
     for (int base = blockIdx.x * kBatchPix + threadIdx.x * 4; base < total; base += gridDim.x * kBatchPix) {
       const int y = base / S, x0 = base - y * S;  // the 4 pixels share row y (S % 4 == 0, base % 4 == 0)
+      float4 r4, g4, b4;
+      pixel(y, x0, r4.x, g4.x, b4.x);
+      pixel(y, x0 + 1, r4.y, g4.y, b4.y);
+      pixel(y, x0 + 2, r4.z, g4.z, b4.z);
+      pixel(y, x0 + 3, r4.w, g4.w, b4.w);
+      *reinterpret_cast<float4*>(out + base) = r4;
+      *reinterpret_cast<float4*>(out + total + base) = g4;
+      *reinterpret_cast<float4*>(out + 2 * total + base) = b4;
+    }
+  } else {
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+      const int y = idx / S, x = idx - y * S;
+      float r, g, b;
+      pixel(y, x, r, g, b);
+      out[idx] = r;
+      out[total + idx] = g;
+      out[2 * total + idx] = b;
+    }
+  }
+}
+
+// ---- ragged batch with a pixel format per frame --------------------------------------------------------------
+// image_batch_pad_resize_kernel with desc [n,5] = (byte offset, h, w, flip, ME_PIXFMT_*): what a camera or a decoder hands
+// over (run_mp.py:50 reads BGR from cv2.VideoCapture, USB cameras give YUYV, video decoders NV12) goes to the RGB planes
+// without a host conversion pass.  h, w are the picture's size in pixels.  The format is uniform per blockIdx.y, so the
+// switch below is a scalar branch; everything around the fetch is the kernel above, operation for operation.
+// YUV -> RGB: the integer limited-range BT.601 conversion of cv2.cvtColor(COLOR_YUV2RGB_NV12 / _YUY2), 20 fractional bits;
+// int32 holds every intermediate (about -161 M .. +560 M); >> is arithmetic.  Chroma is not interpolated.
+__device__ inline int clamp_u8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+__device__ inline void yuv_to_rgb(int Y, int U, int V, int& r, int& g, int& b) {
+  const int y = (Y > 16 ? Y - 16 : 0) * 1220542, u = U - 128, v = V - 128;
+  r = clamp_u8((y + (1 << 19) + 1673527 * v) >> 20);
+  g = clamp_u8((y + (1 << 19) - 852492 * v - 409993 * u) >> 20);
+  b = clamp_u8((y + (1 << 19) + 2116026 * u) >> 20);
+}
+
+__global__ __launch_bounds__(256) void image_batch_formats_kernel(const unsigned char* __restrict__ src,
+                                                                  long long src_bytes,
+                                                                  const long long* __restrict__ desc,
+                                                                  float* __restrict__ dst, int S) {
+  const int f = blockIdx.y;
+  const long long off = desc[5 * f], h64 = desc[5 * f + 1], w64 = desc[5 * f + 2], fmt64 = desc[5 * f + 4];
+  const int flip = desc[5 * f + 3] != 0;
+  // a descriptor that does not lie inside the packed buffer, names no format or breaks its format's parity rule reads
+  // nothing: the frame comes out as padding.  The size test divides, so that no product of descriptor values can overflow.
+  bool valid = h64 > 0 && w64 > 0 && h64 <= (1ll << 30) && w64 <= (1ll << 30) && off >= 0 && off <= src_bytes;
+  const long long avail = src_bytes - off;
+  if (fmt64 == ME_PIXFMT_RGB || fmt64 == ME_PIXFMT_BGR)
+    valid = valid && h64 <= avail / (3 * w64);
+  else if (fmt64 == ME_PIXFMT_NV12)   // hw + hw/2 = (h/2) rows pairs of 3w bytes
+    valid = valid && (h64 & 1) == 0 && (w64 & 1) == 0 && h64 / 2 <= avail / (3 * w64);
+  else if (fmt64 == ME_PIXFMT_YUYV)
+    valid = valid && (w64 & 1) == 0 && h64 <= avail / (2 * w64);
+  else
+    valid = false;
+  const int h = valid ? (int)h64 : 1, w = valid ? (int)w64 : 1, fmt = (int)fmt64;
+  const int P = h > w ? h : w;
+  const int diff = h > w ? h - w : w - h;
+  const int pad1 = diff / 2;
+  const int pad_top = h <= w ? pad1 : 0, pad_left = h <= w ? 0 : pad1;
+  const float scale = (float)P / (float)S;
+  const int total = S * S;
+  const unsigned char* frame = src + (valid ? off : 0);
+  float* out = dst + (size_t)f * 3 * total;
+  auto pixel = [&](int y, int x, float& r, float& g, float& b) {
+    int py = P == S ? y : (int)floorf((float)y * scale);
+    int px = P == S ? x : (int)floorf((float)x * scale);
+    py = py < P - 1 ? py : P - 1;
+    px = px < P - 1 ? px : P - 1;
+    if (flip) px = P - 1 - px;
+    const int sy = py - pad_top, sx = px - pad_left;
+    r = 0.f, g = 0.f, b = 0.f;
+    if (valid && (unsigned)sy < (unsigned)h && (unsigned)sx < (unsigned)w) {
+      int ri, gi, bi;
+      if (fmt == ME_PIXFMT_RGB || fmt == ME_PIXFMT_BGR) {
+        const unsigned char* p = frame + ((size_t)sy * w + sx) * 3;
+        ri = fmt == ME_PIXFMT_RGB ? p[0] : p[2];
+        gi = p[1];
+        bi = fmt == ME_PIXFMT_RGB ? p[2] : p[0];
+      } else if (fmt == ME_PIXFMT_NV12) {   // Y plane [h,w], then the interleaved UV plane [h/2,w]
+        const unsigned char* uv = frame + (size_t)h * w + (size_t)(sy >> 1) * w + (sx & ~1);
+        yuv_to_rgb(frame[(size_t)sy * w + sx], uv[0], uv[1], ri, gi, bi);
+      } else {                              // YUYV: rows of Y0 U Y1 V
+        const unsigned char* row = frame + (size_t)sy * w * 2;
+        const int c = 4 * (sx >> 1);
+        yuv_to_rgb(row[2 * sx], row[c + 1], row[c + 3], ri, gi, bi);
+      }
+      r = (float)ri / 255.f;
+      g = (float)gi / 255.f;
+      b = (float)bi / 255.f;
+    }
+  };
+  if ((S & 3) == 0) {
+    for (int base = blockIdx.x * kBatchPix + threadIdx.x * 4; base < total; base += gridDim.x * kBatchPix) {
+      const int y = base / S, x0 = base - y * S;
       float4 r4, g4, b4;
       pixel(y, x0, r4.x, g4.x, b4.x);
       pixel(y, x0 + 1, r4.y, g4.y, b4.y);
@@ -248,6 +347,22 @@ int me_image_batch_pad_resize_flip_u8_f32(const uint8_t* src, int64_t src_bytes,
   hipLaunchKernelGGL(image_batch_pad_resize_kernel, dim3(tiles, n), dim3(256), 0, (hipStream_t)stream, src,
                      (long long)src_bytes, reinterpret_cast<const long long*>(desc), dst, size);
   return me::check_launch("image_batch_pad_resize_kernel");
+}
+
+int me_image_batch_formats_u8_f32(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int32_t n, float* dst,
+                                  int32_t size, void* stream) {
+  if (n == 0) return 0;
+  ME_REQUIRE(src && desc && dst, ME_E_NULLPTR, "me_image_batch_formats_u8_f32: null pointer");
+  ME_REQUIRE(n > 0 && n <= 65535 && size > 0 && src_bytes > 0, ME_E_BADARG,
+             "me_image_batch_formats_u8_f32: bad n / size / src_bytes");
+  ME_REQUIRE((long long)size * size < (1ll << 30), ME_E_TOOBIG, "me_image_batch_formats_u8_f32: output too large");
+  ME_REQUIRE((size & 3) != 0 || me::aligned16(dst), ME_E_ALIGN, "me_image_batch_formats_u8_f32: dst not 16-byte aligned");
+  const int per_block = (size & 3) == 0 ? kBatchPix : 256;
+  int tiles = (int)me::ceil_div((int64_t)size * size, per_block);
+  if (tiles > 1024) tiles = 1024;
+  hipLaunchKernelGGL(image_batch_formats_kernel, dim3(tiles, n), dim3(256), 0, (hipStream_t)stream, src,
+                     (long long)src_bytes, reinterpret_cast<const long long*>(desc), dst, size);
+  return me::check_launch("image_batch_formats_kernel");
 }
 
 int me_radar_heatmap_f32(const double* points, const int32_t* offsets, const int32_t* sizes, int32_t n,

@@ -27,7 +27,8 @@ from torch.utils.data import Dataset
 
 from .. import hip
 
-__all__ = ["MyDataset", "StagedImages", "StagedRaggedImages", "StagedRadarMaps", "obtain_bboxs"]
+__all__ = ["MyDataset", "StagedImages", "StagedRaggedImages", "StagedRadarMaps", "obtain_bboxs", "PIXEL_FORMATS",
+           "picture_hw"]
 
 _SCENES = ["0", "1", "2", "3", "4"]
 
@@ -120,27 +121,91 @@ class StagedImages:
         return out
 
 
+PIXEL_FORMATS = {"rgb": 0, "bgr": 1, "nv12": 2, "yuyv": 3}   # name -> ME_PIXFMT_* (include/millieye_hip.h)
+
+
+def pixel_format_names(pixel_format, n, what="frame"):
+    """One pixel format name, or one per frame, as a list of ``n`` checked names (:data:`PIXEL_FORMATS`)."""
+    names = list(pixel_format) if isinstance(pixel_format, (list, tuple)) else [pixel_format] * n
+    if len(names) != n:
+        raise hip.MeError(f"{len(names)} pixel formats for {n} {what}s")
+    for i, name in enumerate(names):
+        if not isinstance(name, str) or name not in PIXEL_FORMATS:
+            raise hip.MeError(f"{what} {i}: unknown pixel format {name!r} (one of {', '.join(PIXEL_FORMATS)})")
+    return names
+
+
+def picture_hw(frame, pixel_format="rgb", what="frame"):
+    """Height and width in pixels of the picture a uint8 frame tensor holds in ``pixel_format``: ``"rgb"`` / ``"bgr"``
+    ``[h,w,3]``, ``"yuyv"`` ``[h,w,2]`` (w even), ``"nv12"`` ``[h*3//2, w]`` (h and w even; the Y plane over the interleaved UV
+    plane, the way cv2 and video decoders hand it over).  Raises :class:`hip.MeError` for anything else."""
+    if not isinstance(pixel_format, str) or pixel_format not in PIXEL_FORMATS:
+        raise hip.MeError(f"{what}: unknown pixel format {pixel_format!r} (one of {', '.join(PIXEL_FORMATS)})")
+    shape, dtype = tuple(frame.shape), frame.dtype
+    if pixel_format == "nv12":
+        expected = "uint8 [h*3//2, w] with h and w even"
+        # 3h/2 rows: a row count divisible by 3 is an even h
+        ok = len(shape) == 2 and shape[0] > 0 and shape[0] % 3 == 0 and shape[1] > 0 and shape[1] % 2 == 0
+        hw = (shape[0] // 3 * 2, shape[1]) if ok else None
+    elif pixel_format == "yuyv":
+        expected = "uint8 [h,w,2] with w even"
+        ok = len(shape) == 3 and shape[2] == 2 and shape[0] > 0 and shape[1] > 0 and shape[1] % 2 == 0
+        hw = shape[:2] if ok else None
+    else:
+        expected = "uint8 [h,w,3]"
+        ok = len(shape) == 3 and shape[2] == 3 and shape[0] > 0 and shape[1] > 0
+        hw = shape[:2] if ok else None
+    if not ok or str(dtype) not in ("torch.uint8", "uint8"):   # (a tensor or a numpy array)
+        raise hip.MeError(f"{what}: {pixel_format} expects {expected}, got {dtype} {shape}")
+    return int(hw[0]), int(hw[1])
+
+
 class StagedRaggedImages(StagedImages):
     """A ``StagedImages`` whose ``.to(device)`` builds the whole batch in one launch: every frame's bytes are packed into one
     pinned uint8 buffer and uploaded once, with a ``[n,4]`` int64 descriptor ``(byte offset, h, w, flip)`` per frame, and
     ``me_image_batch_pad_resize_flip_u8_f32`` writes ``[n,3,size,size]`` (bit-identical to the per-frame kernel).  ``.type()``
-    accepts the CUDA float tensor types, for callers that write ``imgs.type(torch.cuda.FloatTensor)``."""
+    accepts the CUDA float tensor types, for callers that write ``imgs.type(torch.cuda.FloatTensor)``.
 
-    packed = desc = None   # set by pack(): the frames' bytes in one uint8 buffer and the [n,4] int64 descriptor
+    ``formats``: one name of :data:`PIXEL_FORMATS` or one per frame - the frames are what a camera or a decoder hands over
+    (shapes: :func:`picture_hw`), their native bytes are packed, the descriptor is ``[n,5]`` ``(byte offset, h, w, flip,
+    format id)`` with the picture's ``h, w``, and ``me_image_batch_formats_u8_f32`` converts on the device: a frame gives the
+    bits its RGB conversion gives on the default path.  ``formats=None`` is the default path."""
+
+    packed = desc = None   # set by pack(): the frames' bytes in one uint8 buffer and the [n,4] ([n,5]) int64 descriptor
+    formats = None         # None: packed RGB and the [n,4] descriptor; else one checked name per frame
+
+    def __init__(self, frames, size, flips=None, formats=None):
+        super().__init__(frames, size, flips)
+        if formats is not None:
+            self.formats = pixel_format_names(formats, len(self.frames))
+            self.frames = [torch.as_tensor(f) for f in self.frames]
+
+    def _format_descriptor(self):
+        """The ``[n,5]`` descriptor of the native frames and their byte total; checks every frame (:func:`picture_hw`)."""
+        desc = torch.empty((len(self.frames), 5), dtype=torch.int64)
+        total = 0
+        for i, (frame, name) in enumerate(zip(self.frames, self.formats)):
+            h, w = picture_hw(frame, name, f"frame {i}")
+            desc[i] = torch.tensor([total, h, w, int(self.flips[i]), PIXEL_FORMATS[name]])
+            total += frame.numel()
+        return desc, total
 
     def pack(self, pin=False, keep_frames=True):
         """The host half of :meth:`to`, callable ahead of time and without a GPU (``pin=False``): checks the frames and copies
         their bytes into one buffer.  The object then carries ``packed`` / ``desc`` (through pickle too) and :meth:`to` only
         uploads them; ``keep_frames=False`` drops the per-frame tensors so that the bytes travel once."""
         n = len(self.frames)
-        desc = torch.empty((n, 4), dtype=torch.int64)
-        total = 0
-        for i, frame in enumerate(self.frames):
-            h, w, c = frame.shape
-            if c != 3 or frame.dtype != torch.uint8 or h <= 0 or w <= 0:
-                raise hip.MeError(f"frame {i}: expected uint8 [h,w,3], got {frame.dtype} {tuple(frame.shape)}")
-            desc[i, 0], desc[i, 1], desc[i, 2], desc[i, 3] = total, h, w, int(self.flips[i])
-            total += h * w * 3
+        if self.formats is not None:
+            desc, total = self._format_descriptor()
+        else:
+            desc = torch.empty((n, 4), dtype=torch.int64)
+            total = 0
+            for i, frame in enumerate(self.frames):
+                h, w, c = frame.shape
+                if c != 3 or frame.dtype != torch.uint8 or h <= 0 or w <= 0:
+                    raise hip.MeError(f"frame {i}: expected uint8 [h,w,3], got {frame.dtype} {tuple(frame.shape)}")
+                desc[i, 0], desc[i, 1], desc[i, 2], desc[i, 3] = total, h, w, int(self.flips[i])
+                total += h * w * 3
         packed = torch.empty((total,), dtype=torch.uint8, pin_memory=pin)
         for i, frame in enumerate(self.frames):
             start = int(desc[i, 0])
@@ -161,11 +226,16 @@ class StagedRaggedImages(StagedImages):
         out = torch.empty(tuple(self.shape), device=device, dtype=torch.float32)
         if n == 0:
             return out
-        src = self if self.packed is not None else StagedRaggedImages(self.frames, self.size, self.flips).pack(pin=True)
+        src = self if self.packed is not None else StagedRaggedImages(self.frames, self.size, self.flips,
+                                                                      self.formats).pack(pin=True)
         packed, desc = src.packed, src.desc
         total = int(packed.numel())
         d_src = packed.to(device, non_blocking=True)
         d_desc = desc.pin_memory().to(device, non_blocking=True)
+        if self.formats is not None:
+            hip.check(hip.lib().me_image_batch_formats_u8_f32(d_src.data_ptr(), total, d_desc.data_ptr(), n, out.data_ptr(),
+                                                              self.size, hip.stream_ptr()), "me_image_batch_formats_u8_f32")
+            return out
         hip.check(hip.lib().me_image_batch_pad_resize_flip_u8_f32(d_src.data_ptr(), total, d_desc.data_ptr(), n,
                                                                    out.data_ptr(), self.size, hip.stream_ptr()),
                   "me_image_batch_pad_resize_flip_u8_f32")

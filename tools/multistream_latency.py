@@ -18,7 +18,12 @@ synchronised - and "step" the whole step with either tail.  The last lines run t
 
 ``--split frame_modes`` builds every fuser of those rows with ``MultiStreamFuser(split="frame_modes")`` (one forward with per-frame
 modes); ``--split compare`` prints only the A/B of the two splits (:func:`compare_splits`; profiles/multistream_frame_modes.txt):
-python tools/multistream_latency.py --split compare --streams 8 32 --steps 40 --out profiles/multistream_frame_modes.txt"""
+python tools/multistream_latency.py --split compare --streams 8 32 --steps 40 --out profiles/multistream_frame_modes.txt
+
+``--pixel-format rgb nv12 yuyv`` prints only the comparison of the input formats (:func:`compare_formats`;
+profiles/multistream_pixel_formats.txt): per network and S the bytes a step packs, the time from the packed payload to the device
+batch, the whole in-process step and the two-process pipeline, every format in the same process, in blocks whose order rotates:
+python tools/multistream_latency.py --pixel-format rgb nv12 yuyv --streams 8 32 --steps 40 --out profiles/multistream_pixel_formats.txt"""
 import argparse
 import os
 import statistics
@@ -50,6 +55,109 @@ class DarkSource:
         frames = [(synth.uniform(f"ms/frame{s}", (480, 640, 3)) * 25).astype(np.uint8) for s in range(self.n)]
         for f in range(self.steps):
             yield frames, [[radar_points((f + 7 * s) % 45)] for s in range(self.n)]
+
+
+def dark_native_frame(fmt, s, h=480, w=640):
+    """Dark ``h x w`` frame of stream ``s`` the way a camera hands it over in ``fmt``: rgb / bgr bytes 0 .. 24 (the frames of the
+    "dark" rows), luma 16 .. 40 under near-neutral chroma for nv12 ``[h*3//2, w]`` / yuyv ``[h,w,2]`` - all select fusion."""
+    if fmt in ("rgb", "bgr"):
+        return (synth.uniform(f"ms/frame{s}", (h, w, 3)) * 25).astype(np.uint8)
+    luma = (16 + synth.uniform(f"ms/luma{s}", (h, w)) * 25).astype(np.uint8)
+    if fmt == "nv12":
+        chroma = (120 + synth.uniform(f"ms/chroma{s}", (h // 2, w)) * 17).astype(np.uint8)
+        return np.concatenate([luma, chroma], 0)
+    chroma = (120 + synth.uniform(f"ms/chroma{s}", (h, w)) * 17).astype(np.uint8)
+    return np.stack([luma, chroma], -1)
+
+
+class NativeDarkSource:
+    """Picklable source of the pipeline rows of :func:`compare_formats`: ``steps`` steps of ``n`` dark frames in ``fmt``."""
+
+    def __init__(self, steps, n, fmt):
+        self.steps, self.n, self.fmt = steps, n, fmt
+
+    def __call__(self):
+        frames = [dark_native_frame(self.fmt, s) for s in range(self.n)]
+        for f in range(self.steps):
+            yield frames, [[radar_points((f + 7 * s) % 45)] for s in range(self.n)]
+
+
+def timed_rotating(fns, steps, repeats):
+    """``timed_ab`` for any number of variants: a block of each per repeat, the order rotating by one every repeat.  Returns per
+    variant the list of its blocks' seconds per step."""
+    out = [[] for _ in fns]
+    k = len(fns)
+    for r in range(repeats):
+        for i in [(r + j) % k for j in range(k)]:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for f in range(steps):
+                fns[i](f)
+            torch.cuda.synchronize()
+            out[i].append((time.perf_counter() - t0) / steps)
+    return out
+
+
+def _spread(blocks, scale=1e3):
+    return f"{statistics.median(blocks) * scale:7.3f} ({min(blocks) * scale:7.3f} .. {max(blocks) * scale:7.3f})"
+
+
+def compare_formats(args, say):
+    """``--pixel-format``: the input formats against the first one named (rgb) in one process.  Per network and S, every
+    format's fuser sees frames of the same picture size (480x640, dark: one forward at batch S) and the same radar streams.
+
+    bytes/step: what ``prepare(pack=True)`` packs - what the pipeline queues and the consumer uploads.  "to device": from that
+    packed payload to the ``[S,3,416,416]`` batch on the device (``StagedRaggedImages.to``: the upload from pageable memory and the
+    launch), device synchronised around every block.  "step": the whole in-process step from the caller's frames (``prepare``
+    without packing, then ``infer``: the bytes are packed into pinned memory and uploaded).  "pipeline": ``FusionPipeline``, every
+    step inferred, the first step (spawn, rendezvous) left out, one run per format and pass, the passes in opposite order."""
+    fmts = args.pixel_format
+    from millieye_amd.pipeline import FusionPipeline
+    say(f"# {torch.cuda.get_device_name(0)}; 480x640 dark frames; {args.steps} steps per block, {args.repeats} blocks per format in "
+        f"rotating order, median (min .. max) of the blocks in ms, 5 warm-up steps; pipeline: {args.steps} steps per run, "
+        f"two passes in opposite order, steps/s of each")
+    say("# not measured: the cvtColor pass on the host that an integrator with a YUV or BGR camera saves (cv2 is not installed)")
+    for cfg, dtype in args.nets:
+        net = _demo_net(cfg, dtype)
+        for n in args.streams:
+            radar = [[[radar_points((f + 7 * s) % 45)] for s in range(n)] for f in range(args.steps)]
+            frames = {fmt: [dark_native_frame(fmt, s) for s in range(n)] for fmt in fmts}
+            fusers = {fmt: MultiStreamFuser(net, RADAR_CALIB, n, model_mode=3, min_hits=2, pixel_format=fmt) for fmt in fmts}
+            payloads = {fmt: fusers[fmt].prepare(frames[fmt], radar[0], pack=True) for fmt in fmts}
+            for f in range(5):
+                for fmt in fmts:
+                    out = fusers[fmt](frames[fmt], radar[f])
+                    payloads[fmt]["img"].to(fusers[fmt].device)
+            assert all(info["mode"] == 0 for _r, info in out)
+            t_up = timed_rotating([lambda f, fmt=fmt: payloads[fmt]["img"].to(fusers[fmt].device) for fmt in fmts],
+                                  args.steps, args.repeats)
+            t_step = timed_rotating([lambda f, fmt=fmt: fusers[fmt](frames[fmt], radar[f]) for fmt in fmts],
+                                    args.steps, args.repeats)
+            pipe = {fmt: [] for fmt in fmts}
+            if args.pipeline:
+                for order in (fmts, fmts[::-1]):
+                    for fmt in order:
+                        piped = MultiStreamFuser(net, RADAR_CALIB, n, model_mode=3, min_hits=2, pixel_format=fmt)
+                        t0, done = None, 0
+                        for _results, _info in FusionPipeline(piped, NativeDarkSource(args.steps + 1, n, fmt), skip_to_newest=False):
+                            if t0 is None:
+                                torch.cuda.synchronize()
+                                t0 = time.perf_counter()
+                            else:
+                                done += 1
+                        pipe[fmt].append(done / (time.perf_counter() - t0))
+            for i, fmt in enumerate(fmts):
+                nbytes = int(payloads[fmt]["img"].packed.numel())
+                base = int(payloads[fmts[0]]["img"].packed.numel())
+                med_up, med_step = statistics.median(t_up[i]), statistics.median(t_step[i])
+                line = (f"{cfg:16s} {dtype:4s} S={n:2d} {fmt:4s}: {nbytes / 1e6:6.2f} MB/step (x {nbytes / base:4.2f}) | to device "
+                        f"{_spread(t_up[i])} ms ({(med_up / statistics.median(t_up[0]) - 1) * 100:+6.1f} %) | step "
+                        f"{_spread(t_step[i])} ms ({(med_step / statistics.median(t_step[0]) - 1) * 100:+6.1f} %)")
+                if pipe[fmt]:
+                    best = max(pipe[fmt])
+                    line += (f" | pipeline {', '.join(f'{v:6.1f}' for v in pipe[fmt])} steps/s, ratio to the in-process step "
+                             f"{', '.join(f'{v * med_step:4.2f}' for v in pipe[fmt])} (x {best / max(pipe[fmts[0]]):4.2f} of {fmts[0]})")
+                say(line)
 
 
 def timed_ab(fn_a, fn_b, steps, repeats=4):
@@ -156,7 +264,13 @@ def main():
     ap.add_argument("--split", choices=["forwards", "frame_modes", "compare"], default="forwards",
                     help="MultiStreamFuser(split=...) of every fuser; 'compare': only the A/B of the two splits (compare_splits)")
     ap.add_argument("--vary-steps", type=int, default=36, help="--split compare: steps of the run with a changing dark count")
+    ap.add_argument("--pixel-format", nargs="+", default=None, choices=["rgb", "bgr", "nv12", "yuyv"],
+                    help="only the comparison of these input formats against the first one (compare_formats)")
+    ap.add_argument("--repeats", type=int, default=4, help="--pixel-format: blocks per format")
+    ap.add_argument("--nets", nargs="*", default=["yolov3-tiny-12:f32", "yolov3:bf16"],
+                    help="--pixel-format: the cfg:dtype pairs to measure")
     args = ap.parse_args()
+    args.nets = [tuple(v.split(":")) for v in args.nets]
     lines = []
 
     def say(text):
@@ -164,6 +278,12 @@ def main():
         lines.append(text)
 
     say(f"# python tools/multistream_latency.py {' '.join(sys.argv[1:])}".rstrip())
+    if args.pixel_format:
+        compare_formats(args, say)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return
     if args.split == "compare":
         compare_splits(args, say)
         if args.out:
