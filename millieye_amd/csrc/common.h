@@ -38,16 +38,27 @@ inline int store_mode() {
   return mode;
 }
 
+// Fast epilogue of conv_igemm_buf_f32: 1 (default) = 16-byte stores through an LDS transpose, 0 = the 4-byte stores straight
+// from the accumulator layout (MILLIEYE_EPILOGUE16; A/B measurements and the reference of the bit-identity test).
+inline int epilogue16() {
+  static const int on = [] {
+    const char* e = getenv("MILLIEYE_EPILOGUE16");
+    return e ? atoi(e) != 0 : 1;
+  }();
+  return on;
+}
+
 typedef unsigned st_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void store16(void* ptr, uint4 v, int mode) {
   if (mode == 0) {
     *reinterpret_cast<uint4*>(ptr) = v;
   } else {
     st_u32x4 d = {v.x, v.y, v.z, v.w};
+    // (s_nop 1: the compiler does not know that the store reads its data registers after issue, and may overwrite them at once)
     if (mode == 1)
-      asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(ptr), "v"(d) : "memory");
+      asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 1" ::"v"(ptr), "v"(d) : "memory");
     else
-      asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(ptr), "v"(d) : "memory");
+      asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(ptr), "v"(d) : "memory");
   }
 }
 __device__ __forceinline__ void store4(float* ptr, float v, int mode) {

@@ -586,8 +586,16 @@ __device__ __forceinline__ void tile_coords(const ConvP& p, int t, int& tile_m, 
 // that put one or two workgroups on a CU (batch 1 / 8): there a stage is bound by the latency of its DMAs, not by the matrix pipe.
 // MASKED: the instance with the column-class tap masks (me_conv_desc.tap_mask, ABI 10).  A separate instance on purpose: the two
 // scalar tests in the tap walk changed the register allocation of the plain kernel (64 x 64 tile: 63 -> 43 VGPRs, another schedule).
+// Waves per SIMD the register allocation has to leave room for: the instances with one 32 x 32 accumulator block per wave (64 x 64,
+// 128 x 32) put six workgroups of four waves on a CU (3-stage ring: 24 KiB of LDS each), so they must stay within 80 registers.
+// The 128 x 64 tail-split and masked instances likewise keep the four waves their 36 KiB rings allow (the plain one never had them).
+constexpr int buf_min_waves(int bm, int bn, int wr, int wc, int minw, bool hyb_or_masked) {
+  const int per_wave = (bm / wr) * (bn / wc);
+  return minw != 1 ? minw : per_wave == 1024 ? 6 : per_wave == 2048 && hyb_or_masked ? 4 : 1;
+}
+
 template <int BM, int BN, int WR, int WC, int MINW = 1, int BABL = 0, int HYB = 0, int KORD = 0, int DEEP = 0, int MASKED = 0>
-__global__ __launch_bounds__(64 * WR * WC, MINW) void conv_igemm_buf_f32(ConvP p) {
+__global__ __launch_bounds__(64 * WR * WC, buf_min_waves(BM, BN, WR, WC, MINW, HYB || MASKED)) void conv_igemm_buf_f32(ConvP p) {
   constexpr int NW = WR * WC;  // waves per workgroup (4 or 8)
   static_assert(NW == 4 || NW == 8, "4 or 8 waves per workgroup");
   constexpr int BK = 16, NST = DEEP ? (KORD ? 9 : 6) : 3;
@@ -963,6 +971,99 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_igemm_buf_f32(ConvP p
   // of matrix-pipe issue slots, and a 1x1 layer's tile has only 128 MFMAs per wave to amortise them over.
   if (m0 + BM <= p.M && n0 + BN <= p.cout && p.ups == 1 && p.act != ME_ACT_SIGMOID) {
     const float slope = p.act == ME_ACT_LEAKY ? 0.1f : 1.0f;
+    if (p.ep16) {
+      // 16-byte form (p.ep16: y / res rows, scale and shift are float4-addressable).  The accumulator layout puts one output
+      // channel on a lane and 16 rows in its registers, so each wave turns its 32 x 32 blocks round through LDS: the raw
+      // accumulators go out as the row-major [32][32] image (ds_write_b32: the 32 lanes of a half write one row = 32 banks), and
+      // come back as float4 number lane + 64 k (ds_read_b128 over consecutive 16-byte slots) - lane l then owns channels
+      // 4 (l & 7) ... + 3 of rows (l >> 3) + 8 k.  A pitch of 32 floats is conflict-free for both patterns, no padding needed.
+      // Per block: 4 stores (and 4 residual loads, all requested before the transpose) instead of 16 (+ 16); the row address
+      // is a wave-uniform base plus one 32-bit lane offset.  The arithmetic per element is that of the 4-byte form below.
+      //
+      // LDS reuse: the image lives in this wave's own 4 KiB at the start of the stage ring (the ring has at least 6 KiB per
+      // wave).  Other waves may still be reading the last K stage there - or, after a slab read-back, last_flag - hence ONE
+      // barrier: behind it every wave has left the K loop and has consumed last_flag (the branch on it lies before the
+      // barrier), and no DMA is in flight (each wave waited for vmcnt(0) at its last stage and issues none after it).  From here
+      // on a wave touches only its own image, and the LDS serves a wave's requests in order: the reads of a block follow its
+      // writes after lgkmcnt(0), the next block's writes follow those reads.
+      __syncthreads();
+      float* img = smem + wave * 1024;
+      float* wp = img + hh * 128 + r32;  // + ((e & 3) + 8 (e >> 2)) * 32 for register e
+      const float4* rp4 = reinterpret_cast<const float4*>(img) + lane;
+      const int lrow8 = lane >> 3, lcol = 4 * (lane & 7);
+      const unsigned yoff = ((unsigned)lrow8 * (unsigned)p.y_pitch + (unsigned)lcol) * 4u;
+      const unsigned roff = ((unsigned)lrow8 * (unsigned)p.res_pitch + (unsigned)lcol) * 4u;
+      const long long roww = m0 + wr * TM;
+      const int colw = n0 + wc * TN;
+      // wave-uniform 64-bit bases (SGPRs) + 32-bit byte offsets: fill_params keeps the pitches below 2^22 floats
+      char* ybase = reinterpret_cast<char*>(p.y + roww * p.y_pitch + colw);
+      const char* rbase = reinterpret_cast<const char*>(p.res + roww * p.res_pitch + colw);
+      const unsigned ypitch4 = (unsigned)p.y_pitch * 4u, rpitch4 = (unsigned)p.res_pitch * 4u;
+      // RES: with residual; PLAIN: store mode 0 (the store is then plain C++ and takes its row base from SGPRs)
+      auto tile = [&](auto res_c, auto plain_c) {
+        constexpr bool RES = decltype(res_c)::value, PLAIN = decltype(plain_c)::value;
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+          const float4 sc = *reinterpret_cast<const float4*>(p.scale + colw + j * 32 + lcol);
+          const float4 sh = *reinterpret_cast<const float4*>(p.shift + colw + j * 32 + lcol);
+#pragma unroll
+          for (int i = 0; i < MT; ++i) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) wp[((e & 3) + 8 * (e >> 2)) * 32] = acc[i][j][e];
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            // (the residual loads come behind the writes: the 16 accumulator registers are free by now)
+            float4 rr[4];
+            if constexpr (RES) {
+#pragma unroll
+              for (int k = 0; k < 4; ++k) {
+                const unsigned row = (unsigned)(i * 32 + 8 * k) * rpitch4 + j * 128;  // wave-uniform
+                rr[k] = *reinterpret_cast<const float4*>(rbase + (roff + row));
+              }
+            }
+            __builtin_amdgcn_sched_barrier(0);  // (all four requested here, not one by one where they are consumed)
+            float4 v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = rp4[64 * k];
+            asm volatile("" ::: "memory");  // (the next block's writes stay behind these reads)
+            __builtin_amdgcn_sched_barrier(0);
+            auto one = [&](float a, float s, float h) {
+              const float t = a * s + h;
+              return fmaxf(t, t * slope);
+            };
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              float4 o;
+              o.x = one(v[k].x, sc.x, sh.x);
+              o.y = one(v[k].y, sc.y, sh.y);
+              o.z = one(v[k].z, sc.z, sh.z);
+              o.w = one(v[k].w, sc.w, sh.w);
+              if constexpr (RES) {
+                o.x += rr[k].x;
+                o.y += rr[k].y;
+                o.z += rr[k].z;
+                o.w += rr[k].w;
+              }
+              const unsigned row = (unsigned)(i * 32 + 8 * k) * ypitch4 + j * 128;  // wave-uniform
+              me::store16(ybase + (yoff + row), make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(o.w)),
+                          PLAIN ? 0 : p.store_mode);
+              __builtin_amdgcn_sched_barrier(0);  // one row group at a time: the 64 x 64 instance has 64 VGPRs to live in
+            }
+          }
+        }
+      };
+      if (p.store_mode == 0) {
+        if (p.res)
+          tile(std::true_type{}, std::true_type{});
+        else
+          tile(std::false_type{}, std::true_type{});
+      } else {
+        if (p.res)
+          tile(std::true_type{}, std::false_type{});
+        else
+          tile(std::false_type{}, std::false_type{});
+      }
+      return;
+    }
     const long long ystep = p.y_pitch, rstep = p.res_pitch;
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
@@ -1511,6 +1612,11 @@ int fill_params(const me_conv_desc* d, ConvP& p) {
   p.counters_len = p.counters ? d->tile_counters_len : 0;
   p.mask_cols = d->tap_mask_cols > 0 ? d->tap_mask_cols : 0;
   for (int i = 0; i < 4; ++i) p.tapmask[i] = d->tap_mask[i];
+  // 16-byte epilogue of conv_igemm_buf_f32's whole tiles: every float4 it touches must be aligned (a tile starts at a multiple of
+  // 32 channels), and the byte offsets inside a wave's 64 rows must fit 32 bits.  Everything else keeps the 4-byte epilogue.
+  auto rows16 = [](const float* ptr, long long pitch) { return me::aligned16(ptr) && pitch % 4 == 0 && pitch < (1ll << 22); };
+  p.ep16 = me::epilogue16() && d->upsample == 1 && d->act != ME_ACT_SIGMOID && rows16(d->y, d->y_pitch) &&
+           (!d->res || rows16(d->res, d->res_pitch)) && me::aligned16(d->scale) && me::aligned16(d->shift);
   return 0;
 }
 

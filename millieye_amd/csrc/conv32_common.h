@@ -34,6 +34,7 @@ struct ConvP {
   int store_mode;  // me::store_mode(): output stores of the fast epilogue plain (0) or streaming (nt)
   unsigned tapmask[4];  // me_conv_desc.tap_mask: set taps of the four column classes (conv_igemm_buf_f32, tap-major walk)
   int mask_cols;        // output channels per column class, 0 = no masks
+  int ep16;             // conv_igemm_buf_f32: whole tiles store 16 bytes per lane through the LDS transpose (fill_params)
 };
 
 __device__ __forceinline__ float apply_act(float v, int act) {
