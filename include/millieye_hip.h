@@ -206,6 +206,39 @@ int me_nms_batched_prepped_f32(const me_nms_desc* d, void* stream);
 int me_nms_candidate_counts(const void* workspace, int32_t n, int32_t rows, int32_t* cand_count, int32_t* fallback,
                             void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * me_nms_python_f32 - the reference's Python NMS: +1-pixel IoU, labels compared by equality, no cap on the kept rows,
+ *   optional box merging (csrc/nms_py.hip).
+ * replaces: non_max_suppression of module3_our_dataset/utils/utils.py:281-334 (= module2_mixed/utils/utils.py; score_mode 0,
+ *   inclusive 0, merge 0) and of module3_our_dataset/yolov3/utils/utils.py:231-293 (score_mode 1, inclusive 1, merge 1), with
+ *   bbox_iou (utils/utils.py:248-278) and xywh2xyxy (:68-74); fp32, contraction off, the reference's operation order.
+ * pred: [n, rows, 5+C] (cx,cy,w,h,obj,cls...).  If writeback_xyxy != 0 the first four columns of EVERY row are overwritten with
+ *   (x1,y1,x2,y2) = c -+ w / 2, like the reference does in place.  Candidates: rows with obj >= conf_thresh (a NaN drops out).
+ *   cls_conf / cls_pred: torch.max(1).  Order: descending obj (score_mode 0) or obj * cls_conf (score_mode 1, one fp32 product);
+ *   ties -> lower row first.  Walk: the first alive candidate i is kept and removes every alive j with label_j == label_i and
+ *   iou(i,j) > iou_thresh (inclusive != 0: >=), inter = max(min(x2)-max(x1)+1, 0) * max(min(y2)-max(y1)+1, 0),
+ *   area = (x2-x1+1)*(y2-y1+1), iou = inter / (((a_i+a_j) - inter) + 1e-16f).  merge != 0: the keeper's box becomes
+ *   sum(obj_j * box_j) / sum(obj_j) over the set it removes at its turn, itself included (summed in float64 in a fixed order:
+ *   two calls give the same bits); the test always uses the un-merged boxes.
+ * ONE DEPARTURE from the reference: the keeper always removes itself.  The reference never ends when the top box fails its own
+ *   test (NaN coordinates, w + 1 <= 0, iou_thresh >= 1); here such a box is kept once and, under merge, is a cluster of one.
+ * det: [n, rows, 7] rows (x1,y1,x2,y2,obj,cls_conf,cls_pred) in kept order; count[n] valid rows each (the rest is untouched).
+ * workspace: me_nms_python_workspace_bytes(n, rows) bytes, 256-byte aligned, contents irrelevant.
+ * capacity: rows <= 32768; every row may be a candidate and every candidate a kept row.  No host synchronisation.
+ */
+typedef struct me_nms_python_desc {
+  float* pred;
+  float* det;
+  int32_t* count;
+  void* workspace;
+  int32_t n, rows, num_classes;
+  float conf_thresh, iou_thresh;
+  int32_t score_mode, inclusive, merge;
+  int32_t writeback_xyxy;
+} me_nms_python_desc;
+int64_t me_nms_python_workspace_bytes(int32_t n, int32_t rows);
+int me_nms_python_f32(const me_nms_python_desc* d, void* stream);
+
 /* plain torchvision-style nms / batched_nms on explicit boxes (box_ops.* re-export used by
  *   run_sp.py:214 / run_mp.py:320).  boxes [m,4] xyxy, scores [m], labels [m] (float class ids,
  *   may be NULL -> plain nms).  keep[m] receives kept indices in descending-score order,
@@ -892,7 +925,7 @@ int me_adam_step_f32(const me_adam_desc* d, void* stream);
 int32_t me_adam_chunk(void);
 
 /* sizes of the descriptor structs, so a binding can assert its mirror layout */
-int32_t me_sizeof(int32_t which); /* 0 conv, 1 pool, 2 yolo, 3 nms, 4 heads, 5 heads_weights, 6 conv16, 7 pack, 8 bneck16, 9 adam, 10 radar */
+int32_t me_sizeof(int32_t which); /* 0 conv, 1 pool, 2 yolo, 3 nms, 4 heads, 5 heads_weights, 6 conv16, 7 pack, 8 bneck16, 9 adam, 10 radar, 11 nms_python */
 
 #ifdef __cplusplus
 }

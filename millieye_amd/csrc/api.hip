@@ -43,6 +43,7 @@ int32_t me_sizeof(int32_t which) {
     case 8: return (int32_t)sizeof(me_bneck16_desc);
     case 9: return (int32_t)sizeof(me_adam_desc);
     case 10: return (int32_t)sizeof(me_radar_desc);
+    case 11: return (int32_t)sizeof(me_nms_python_desc);
     default: return -1;
   }
 }

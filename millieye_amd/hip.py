@@ -90,6 +90,22 @@ class NmsDesc(C.Structure):
     ]
 
 
+class NmsPythonDesc(C.Structure):
+    """me_nms_python_desc: the reference's Python NMS (csrc/nms_py.hip)."""
+    _fields_ = [
+        ("pred", C.c_void_p), ("det", C.c_void_p), ("count", C.c_void_p), ("workspace", C.c_void_p),
+        ("n", C.c_int32), ("rows", C.c_int32), ("num_classes", C.c_int32),
+        ("conf_thresh", C.c_float), ("iou_thresh", C.c_float),
+        ("score_mode", C.c_int32), ("inclusive", C.c_int32), ("merge", C.c_int32),
+        ("writeback_xyxy", C.c_int32),
+    ]
+
+
+# sizes of csrc/nms_py.hip a test of me_nms_python_f32 wants both sides of: sorted candidates per round (TILE), earlier keepers per
+# pynms_cross workgroup (KCHUNK), and the capacity
+PYNMS_TILE, PYNMS_KEEPER_CHUNK, PYNMS_MAX_ROWS = 1024, 256, 32768
+
+
 class HeadsWeights(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in (
         "w0t", "b0", "w1", "b1", "w2", "b2", "rw", "rscale", "rshift", "rw2", "rb2", "e1w", "e1b", "e2w", "e2b",
@@ -178,7 +194,7 @@ class AdamDesc(C.Structure):
 
 
 _STRUCTS = {0: ConvDesc, 1: PoolDesc, 2: YoloDesc, 3: NmsDesc, 4: HeadsDesc, 5: HeadsWeights, 6: Conv16Desc, 7: PackDesc,
-            8: Bneck16Desc, 9: AdamDesc, 10: RadarDesc}
+            8: Bneck16Desc, 9: AdamDesc, 10: RadarDesc, 11: NmsPythonDesc}
 
 # name -> (restype, argtypes); every symbol include/millieye_hip.h declares
 SIGNATURES = {
@@ -234,6 +250,8 @@ SIGNATURES = {
     "me_nms_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "me_nms_candidate_counts": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "me_nms_batched_f32": (C.c_int, [C.POINTER(NmsDesc), C.c_void_p]),
+    "me_nms_python_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "me_nms_python_f32": (C.c_int, [C.POINTER(NmsPythonDesc), C.c_void_p]),
     "me_nms_boxes_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "me_nms_boxes_grouped_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
@@ -865,6 +883,34 @@ def nms_batched(pred, conf_thresh, iou_thresh, max_det, writeback_xyxy=True, pre
         check(lib().me_nms_batched_prepped_f32(C.byref(d), stream_ptr()), "me_nms_batched_prepped_f32")
     else:
         check(lib().me_nms_batched_f32(C.byref(d), stream_ptr()), "me_nms_batched_f32")
+    return det, count
+
+
+def nms_python(pred, conf_thresh, iou_thresh, score_mode, inclusive, merge, writeback_xyxy=True):
+    """The reference's Python NMS (``me_nms_python_f32``: +1-pixel IoU, label equality, no cap on the kept rows): pred [N,R,5+C]
+    (its first four columns become xyxy in place when ``writeback_xyxy``) -> (det [N,R,7], count int32 [N]) on the device; rows >=
+    count are unspecified.  ``score_mode`` 0 ranks by objectness, 1 by ``obj * cls_conf``; ``inclusive`` removes at ``iou >= thr``
+    instead of ``iou > thr``; ``merge`` replaces a kept box by the objectness-weighted mean of the boxes it removes, itself included.
+    Unlike the reference, a kept box always removes itself (the reference never ends when the top box fails its own test)."""
+    _require_cuda_f32(pred, "prediction")
+    if not pred.is_contiguous():
+        raise MeError("prediction must be contiguous")
+    if pred.dim() != 3 or pred.shape[2] < 5:
+        raise MeError(f"prediction must be [N,R,5+C] (got {tuple(pred.shape)})")
+    n, rows, per = pred.shape
+    det = torch.empty((n, rows, 7), device=pred.device, dtype=torch.float32)
+    count = torch.empty((n,), device=pred.device, dtype=torch.int32)
+    if n == 0 or rows == 0:
+        return det, count.zero_()
+    d = NmsPythonDesc()
+    d.n, d.rows, d.num_classes = n, rows, per - 5
+    d.conf_thresh, d.iou_thresh = conf_thresh, iou_thresh
+    d.score_mode, d.inclusive, d.merge = int(score_mode), 1 if inclusive else 0, 1 if merge else 0
+    d.writeback_xyxy = 1 if writeback_xyxy else 0
+    nbytes = lib().me_nms_python_workspace_bytes(n, rows)  # 0 past the capacity: the call below refuses with the reason
+    ws_ptr, _keep = _workspace(max(nbytes, 256), pred.device, slot="nms_python")
+    d.pred, d.det, d.count, d.workspace = pred.data_ptr(), det.data_ptr(), count.data_ptr(), ws_ptr
+    check(lib().me_nms_python_f32(C.byref(d), stream_ptr()), "me_nms_python_f32")
     return det, count
 
 

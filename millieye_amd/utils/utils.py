@@ -248,7 +248,7 @@ def get_batch_statistics(outputs, targets, iou_threshold):
 
 
 # --------------------------------------------------------------------------------------
-# NMS (reference utils/utils.py:337-378 + torchvision.ops.boxes.batched_nms)
+# NMS (reference utils/utils.py:337-378 + torchvision.ops.boxes.batched_nms; the Python NMS of :281-334)
 # --------------------------------------------------------------------------------------
 class _BoxOps:
     """Stand-in for ``torchvision.ops.boxes`` (the reference's ``box_ops`` re-export,
@@ -293,14 +293,40 @@ def non_max_suppression_cpp(prediction, conf_thresh, nms_thresh=0.5, detections_
     return out
 
 
+def python_nms(prediction, conf_thresh, nms_thresh, score_mode, inclusive, merge):
+    """The two Python NMS functions of the reference on ``me_nms_python_f32``: a list of ``[k,7]`` tensors on
+    ``prediction.device`` (``None`` for an image without candidates); a CPU ``prediction`` is staged to the GPU and gets its
+    first four columns written back as xyxy."""
+    src_device = prediction.device
+    dev_pred = prediction if prediction.is_cuda else prediction.to(_hip.default_device())
+    dense, counts = _hip.nms_python(dev_pred, float(conf_thresh), float(nms_thresh), score_mode, inclusive, merge,
+                                    writeback_xyxy=True)
+    if dev_pred is not prediction:
+        prediction[..., :4] = dev_pred[..., :4].to(src_device)
+    counts_host = counts.tolist()  # the one host sync of this API (list lengths are data dependent)
+    out = [None] * len(counts_host)
+    for i, n in enumerate(counts_host):
+        if n > 0:
+            out[i] = dense[i, :n] if dev_pred is prediction else dense[i, :n].to(src_device)
+    return out
+
+
 def non_max_suppression(prediction, conf_thresh=0.01, nms_thresh=0.5):
-    """Legacy API of the reference (``utils/utils.py:281-334``: +1-pixel IoU, rows
-    ``[n,7]``).  Not on the hot path (no m2/m3 script calls it); kept for name
-    compatibility and implemented on top of the same device kernel is *not* possible
-    (different IoU convention), so it is deliberately unsupported."""
-    raise NotImplementedError(
-        "non_max_suppression (python NMS with +1 IoU) is off the accelerated path; "
-        "use non_max_suppression_cpp like module3_our_dataset/my_models.py:457 does")
+    """Confidence filter + the reference's Python NMS, no cap on the kept boxes.
+
+    Mirror of reference ``utils/utils.py:281-334`` (module3_our_dataset and module2_mixed: the two copies differ by one
+    comment): ``prediction`` ``[N,R,5+C]`` with (cx,cy,w,h,obj,cls...) rows; its first four columns are converted to xyxy
+    **in place** on every row; candidates are the rows with ``obj >= conf_thresh``, ranked by objectness (ties: lower row
+    first); the best alive box is kept and removes every alive box of the same ``cls_pred`` whose **+1-pixel** IoU with it
+    (:func:`bbox_iou`) is ``> nms_thresh``.  Returns a list of ``[k,7]`` tensors (x1,y1,x2,y2,obj,cls_conf,cls_pred) on
+    ``prediction.device`` or ``None`` for images without candidates.
+
+    One departure from the reference: a kept box always removes itself.  The reference loops forever when the top box
+    fails its own test (NaN coordinates, ``w + 1 <= 0``, ``nms_thresh >= 1``); here such a box is kept once.
+
+    The work runs in the ``me_nms_python_f32`` HIP kernels (``csrc/nms_py.hip``); a CPU ``prediction`` is staged to the GPU
+    and the results copied back."""
+    return python_nms(prediction, conf_thresh, nms_thresh, score_mode=0, inclusive=False, merge=False)
 
 
 # --------------------------------------------------------------------------------------
