@@ -6,7 +6,7 @@
 // arithmetic below uses the same operation order with FP contraction off, comparisons are
 // written as the C++ std::max / std::min the CPU kernel uses (NaN behaviour included).
 //
-// Round 3: up to MATN (4096) candidates per image the selection is no longer one workgroup's serial argmax loop but the
+// Round 3: up to MATN (1024) candidates per image the selection is no longer one workgroup's serial argmax loop but the
 // whole chip's work (BASELINE north_star: "wavefront ballot / reduce for NMS"):
 //   nms_rank    sorts an image's candidates by key (rank = number of larger keys, 256 candidates per workgroup) and writes
 //               the sorted offset boxes (boxes + label * (max + 1); the maximum comes from nms_prep's atomics);
@@ -113,8 +113,12 @@ __device__ __forceinline__ unsigned sortable(float f) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// The order of torch.sort(descending) with the oracle's tie rule: every NaN score shares the top key, above +inf, whatever its
+// sign bit and payload (sortable() alone ranks a sign-bit NaN - what 0 / 0 gives on x86 - below -inf and orders NaNs by payload),
+// and -0 takes +0's key (they compare equal).  Among equal high words the row word decides: the lower row first.
 __device__ __forceinline__ unsigned long long make_key(float score, int row) {
-  return ((unsigned long long)sortable(score) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)row);
+  const unsigned hi = (score != score) ? 0xFFFFFFFFu : sortable(score + 0.f);
+  return ((unsigned long long)hi << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)row);
 }
 
 // boxes.max() of batched_nms's offset trick, gathered while the candidates are appended: the largest non-NaN coordinate as

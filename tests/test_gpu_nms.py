@@ -60,10 +60,12 @@ def test_nms_matches_oracle_bitexact(hip_lib, n, rows, nc, thr):
 
 
 def test_nms_capped_matrix_falls_back_when_it_runs_out(hip_lib):
-    """The multi-workgroup path looks at the 1024 best-scored candidates of an image; when those do not yield max_det
-    winners and more candidates exist (here: 3000 candidates in 60 tight clusters - every cluster keeps one box, so the walk
-    has to visit all of them), the image is redone by the single-workgroup kernel.  Both images of the batch must equal the
-    oracle bit for bit: image 0 takes the fallback, image 1 (300 well separated boxes) does not."""
+    """The multi-workgroup path builds its bit matrix for the 1024 best-scored candidates of an image; when those do not yield
+    max_det winners and more candidates exist (here: 3000 candidates in 60 tight clusters - every cluster keeps one box, so the
+    walk has to visit all of them), nms_scan_kernel's continuation walks the rest of the sorted list (max_det = 200 is within
+    CONT_KEEP = 1024; a larger max_det would hand the image to the single-workgroup kernel, and the name of this test dates
+    from when every such image went there).  Both images of the batch must equal the oracle bit for bit: image 0 takes the
+    continuation, image 1 (300 well separated boxes) ends inside the matrix; neither sets its fallback flag."""
     from millieye_amd import hip
     n, rows, nc = 2, 3200, 4
     g = np.random.RandomState(5)
@@ -81,6 +83,12 @@ def test_nms_capped_matrix_falls_back_when_it_runs_out(hip_lib):
     pred = torch.from_numpy(pred)
     ref, _ = _oracle_nms_cpp(pred, 0.1)
     det, cnt = hip.nms_batched(pred.cuda(), 0.1, 0.5, 200, writeback_xyxy=False)
+    flags = torch.full((2 * n,), -1, dtype=torch.int32, device="cuda")
+    ws, _keepalive = hip.nms_workspace(n, rows, torch.device("cuda"))  # the cached buffer nms_batched has just used
+    hip.check(hip.lib().me_nms_candidate_counts(ws, n, rows, flags.data_ptr(), flags[n:].data_ptr(), hip.stream_ptr()),
+              "me_nms_candidate_counts")
+    flags = flags.cpu().tolist()
+    assert flags[:n] == [int((pred[i, :, 4] >= 0.1).sum()) for i in range(n)] and flags[n:] == [0, 0], flags
     cnt = cnt.cpu().tolist()
     assert ref[0].shape[0] < 200 and int((pred[0, :, 4] >= 0.1).sum()) > 1024, "image 0 must exhaust the capped list"
     for i in range(n):
