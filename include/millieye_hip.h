@@ -722,6 +722,28 @@ int me_image_batch_pad_resize_flip_u8_f32(const uint8_t* src, int64_t src_bytes,
 #define ME_PIXFMT_YUYV 3
 int me_image_batch_formats_u8_f32(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int32_t n, float* dst,
                                   int32_t size, void* stream);
+/* me_image_batch_area_u8_f32: me_image_batch_formats_u8_f32 - the same src, the same desc [n,5], the same validity rules and
+ * argument checks, one launch, dst [n,3,size,size] with 16-byte stores for size % 4 == 0 - with an AREA-AVERAGING resize in
+ * place of the nearest one.  It generalises the reference's resize() helper (utils/datasets.py:30-32, used at :317) from
+ * F.interpolate(mode="nearest") to mode="area"; the reference's scripts never ask for that, so there is nothing of theirs to
+ * compare with: the result is pinned to torch's float64 F.interpolate(padded_square / 255, size, mode="area") rounded to
+ * float32.  Applied where the nearest resize is: after ToTensor, pad_to_square(img, 0) and the optional mirror of the
+ * padded square.  Exact integer arithmetic:
+ *   P = max(h, w); pad_top / pad_left as above (diff / 2 in front); a padded pixel outside the picture is 0 in every channel.
+ *   Output index i of [0, size) covers the padded indices [a_i, b_i), a_i = floor(i P / size), b_i = ceil((i + 1) P / size)
+ *   (64-bit products, no float), on both axes: neighbouring windows may share a pixel; P == size gives one pixel per window,
+ *   P < size one or two.  With flip, padded column px reads the unmirrored column P - 1 - px.
+ *   Per channel: sum = the int32 sum of the window's uint8 values (padding adds 0), cnt = (b_y - a_y)(b_x - a_x) (padding
+ *   counts), output = (float)sum / (float)(255 * cnt), one IEEE division.
+ *   Formats: every source pixel goes through the integer conversion above to 8-bit R, G, B first (chroma not interpolated,
+ *   BGR swapped) and is summed afterwards: a frame in format F gives the bits its RGB conversion gives.
+ * Range: P <= 255 * size.  Then a window side is at most 256, 255 * cnt <= 16 711 680 < 2^24 and sum <= 255 * cnt: both
+ * operands are exact in float32 and the quotient is the correctly rounded one (at most 2^-25 from the real value).  A frame
+ * beyond that comes out all zero, like every other invalid descriptor (StagedRaggedImages.pack() refuses it on the host).
+ * For P == size the output is bit-identical to me_image_batch_formats_u8_f32's.  The geometry (padded square -> size) is
+ * the nearest path's, so box rescaling is unchanged. */
+int me_image_batch_area_u8_f32(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int32_t n, float* dst,
+                               int32_t size, void* stream);
 int me_radar_heatmap_f32(const double* points, const int32_t* offsets, const int32_t* sizes, int32_t n,
                          int32_t radar_maps_size, float* out, int32_t map_size, void* stream);
 

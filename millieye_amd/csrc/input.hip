@@ -8,11 +8,15 @@
 //   me_image_batch_formats_u8_f32
 //                               the ragged batch with a pixel format per frame (RGB, BGR, NV12, YUYV): the frames a camera
 //                               or a decoder hands over, without the host's conversion to RGB (run_mp.py:50,114).
+//   me_image_batch_area_u8_f32  the same ragged batch with F.interpolate(mode="area") for the resize: an option the reference's
+//                               scripts do not have, pinned to torch's float64 area interpolation (exact integer sums).
 //   me_radar_heatmap_f32        plot_radar_heatmap (:59-106: three np.histogram2d in float64, per-bin means, range
 //                               normalisation) + ToTensor().float() (:267) + pad_to_square (:270) +
 //                               F.interpolate(bilinear, align_corners=True) to the map size (:318-321).
 // Both are HBM/latency-trivial (a 1600x900 frame is 4.3 MB in, 2 MB out); the point is that the batch never
 // exists on the host and the 3 histograms + resize per frame leave the DataLoader's critical path.
+#include <type_traits>
+
 #include "common.h"
 
 // every product / sum below is a separately rounded IEEE operation in the reference (numpy float64, aten float32
@@ -213,6 +217,261 @@ __global__ __launch_bounds__(256) void image_batch_formats_kernel(const unsigned
   }
 }
 
+// ---- ragged batch, area-averaging resize -----------------------------------------------------------------------
+// image_batch_formats_kernel with resize(img, S) = F.interpolate(mode="area") in place of the reference's nearest resize
+// (utils/datasets.py:30-32, :317): adaptive average pooling of the padded, optionally mirrored square, in exact integers.
+// Output index i covers the padded indices [floor(i P / S), ceil((i + 1) P / S)) on each axis (64-bit products); per channel
+// sum = the int32 sum of the window's uint8 values (padding adds 0 and counts), cnt = the window's area and the output is
+// (float)sum / (float)(255 * cnt), one IEEE division.  P <= 255 S keeps 255 cnt < 2^24, so both operands are exact and the
+// quotient is the correctly rounded one; a frame beyond that is invalid and comes out all zero.  Formats go through
+// yuv_to_rgb pixel by pixel BEFORE the sum (the clamps do not commute with it).
+// Unlike the nearest kernels this one reads every source byte.  grid (S, n): a workgroup owns one output row of one frame.
+// Its source rows are read 16 (NV12: 8 + 8) bytes per lane, coalesced along the row, each lane keeping the column sums of
+// its bytes over the window's rows in registers (the vertical half, no cross-lane traffic); the column sums go to LDS once
+// and the horizontal half adds each output's window from there.  Row starts are arbitrary byte addresses (3w-, 2w- and
+// w-byte rows, frames back to back): the loads are unaligned 16-byte loads, which global memory serves on gfx9 and later;
+// only a load that would end behind src_bytes falls back to guarded byte loads.  A row wider than the LDS holds is walked in
+// segments of whole output windows (neighbouring windows may share a column, which is then read twice).
+constexpr int kAreaRgbBytes = 4096;   // RGB / BGR: 256 lanes x 16 bytes of one row per segment
+constexpr int kAreaYuvPix = 2048;     // YUV: 256 lanes x 8 pixels per segment, one LDS plane per channel
+constexpr int kAreaLds = 3 * kAreaYuvPix;
+
+// N bytes at src + at as little-endian dwords.  kWide: one unaligned N-byte load, for a caller that knows at + N <= src_bytes;
+// otherwise byte loads, and a byte at or behind src_bytes reads as 0.
+template <int N, bool kWide>
+__device__ inline void load_bytes(const unsigned char* __restrict__ src, long long at, long long src_bytes,
+                                  unsigned (&v)[N / 4]) {
+  if (kWide) {
+    __builtin_memcpy(v, src + at, N);
+  } else {
+#pragma unroll
+    for (int d = 0; d < N / 4; ++d) {
+      unsigned x = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (at + 4 * d + j < src_bytes) x |= (unsigned)src[at + 4 * d + j] << (8 * j);
+      v[d] = x;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void image_batch_area_kernel(const unsigned char* __restrict__ src, long long src_bytes,
+                                                               const long long* __restrict__ desc,
+                                                               float* __restrict__ dst, int S) {
+  __shared__ int cs[kAreaLds];   // column sums of the segment: RGB / BGR by byte of the row, YUV [channel][pixel]
+  const int f = blockIdx.y, oy = blockIdx.x, t = threadIdx.x;
+  const long long off = desc[5 * f], h64 = desc[5 * f + 1], w64 = desc[5 * f + 2], fmt64 = desc[5 * f + 4];
+  const int flip = desc[5 * f + 3] != 0;
+  // the validity rules of image_batch_formats_kernel, and the range rule P <= 255 S.  S < 2^15 bounds h and w by 2^23
+  // first, so the byte counts below are products that cannot overflow (that kernel divides instead).
+  bool valid = h64 > 0 && w64 > 0 && h64 <= 255ll * S && w64 <= 255ll * S && off >= 0 && off <= src_bytes;
+  const long long avail = src_bytes - off, hw = valid ? h64 * w64 : 0;
+  if (fmt64 == ME_PIXFMT_RGB || fmt64 == ME_PIXFMT_BGR)
+    valid = valid && 3 * hw <= avail;
+  else if (fmt64 == ME_PIXFMT_NV12)
+    valid = valid && (h64 & 1) == 0 && (w64 & 1) == 0 && hw + hw / 2 <= avail;
+  else if (fmt64 == ME_PIXFMT_YUYV)
+    valid = valid && (w64 & 1) == 0 && 2 * hw <= avail;
+  else
+    valid = false;
+  const int h = valid ? (int)h64 : 1, w = valid ? (int)w64 : 1, fmt = (int)fmt64;
+  const bool yuv = fmt == ME_PIXFMT_NV12 || fmt == ME_PIXFMT_YUYV;
+  const int P = h > w ? h : w;
+  const int diff = h > w ? h - w : w - h;
+  const int pad1 = diff / 2;
+  const int pad_top = h <= w ? pad1 : 0, pad_left = h <= w ? 0 : pad1;
+  const int total = S * S;
+  float* out = dst + (size_t)f * 3 * total + (size_t)oy * S;
+  // i P = q S + r.  Every product fits 32 bits for the frames of practice ((S + 1) P < 2^31), where the quotient costs a
+  // fraction of the 64-bit one; a run of outputs divides once and steps (q, r) by (P / S, P % S).
+  const bool small = (long long)(S + 1) * P < (1ll << 31);
+  auto divmod = [&](int i, int& q, int& r) {
+    if (small) {
+      const unsigned n = (unsigned)i * (unsigned)P;
+      q = (int)(n / (unsigned)S), r = (int)(n - (unsigned)q * (unsigned)S);
+    } else {
+      const long long n = (long long)i * P, qq = n / S;
+      q = (int)qq, r = (int)(n - qq * S);
+    }
+  };
+  int qs, rs;
+  divmod(1, qs, rs);
+  auto win_lo = [&](int i) {
+    int q, r;
+    divmod(i, q, r);
+    return q;
+  };
+  auto win_hi = [&](int i) {
+    int q, r;
+    divmod(i + 1, q, r);
+    return q + (r > 0);
+  };
+  const int ay = win_lo(oy), by = win_hi(oy);
+  const int sy0 = ay - pad_top > 0 ? ay - pad_top : 0, sy1 = by - pad_top < h ? by - pad_top : h;   // picture rows
+  // outputs per segment: a multiple of 4 whose windows span at most TX P / S + 2 <= capacity - 1 pixels (one more when
+  // the span is moved to an even start); P <= 255 S leaves room for at least 5
+  const int cap = yuv ? kAreaYuvPix : kAreaRgbBytes / 3;
+  const int tx = (int)((unsigned)((cap - 3) * S) / (unsigned)P) & ~3;   // (S < 2^15: the product stays under 2^26)
+  const int TX = tx < 4 ? 4 : (tx > S ? S : tx);
+  const int cfirst = fmt == ME_PIXFMT_BGR ? 2 : 0, cstep = fmt == ME_PIXFMT_BGR ? -1 : 1;
+  for (int ox0 = 0; ox0 < S; ox0 += TX) {
+    const int ox1 = ox0 + TX < S ? ox0 + TX : S;
+    // the segment's padded columns, before the mirror, and the picture columns among them
+    const int pa = win_lo(ox0), pb = win_hi(ox1 - 1);
+    const int lo = flip ? P - pb : pa, hi = flip ? P - pa : pb;
+    int sx0 = lo - pad_left > 0 ? lo - pad_left : 0;
+    const int sx1 = hi - pad_left < w ? hi - pad_left : w;
+    if (yuv) sx0 &= ~1;   // whole chroma pairs
+    const bool any = valid && sy1 > sy0 && sx1 > sx0;
+    if (any && !yuv) {
+      const int k = 16 * t;
+      if (k < 3 * (sx1 - sx0)) {
+        // two column sums per register, 16 bits each: a window has at most 256 rows (P <= 255 S), 256 * 255 < 2^16
+        unsigned acc[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] = 0;
+        const long long pitch = 3ll * w;
+        long long at = off + sy0 * pitch + 3ll * sx0 + k;
+        auto add = [&](const unsigned (&v)[4]) {
+#pragma unroll
+          for (int d = 0; d < 4; ++d) {
+            acc[2 * d] += v[d] & 0x00ff00ffu;              // bytes 0 and 2
+            acc[2 * d + 1] += (v[d] >> 8) & 0x00ff00ffu;   // bytes 1 and 3
+          }
+        };
+        // the lane's highest address decides once between wide loads and the guarded byte loads (the buffer's last bytes)
+        auto rows = [&](auto wide) {
+          constexpr bool kWide = decltype(wide)::value;
+          int sy = sy0;
+#pragma unroll 1
+          for (; kWide && sy + 4 <= sy1; sy += 4, at += 4 * pitch) {   // four rows in flight
+            unsigned v0[4], v1[4], v2[4], v3[4];
+            load_bytes<16, kWide>(src, at, src_bytes, v0);
+            load_bytes<16, kWide>(src, at + pitch, src_bytes, v1);
+            load_bytes<16, kWide>(src, at + 2 * pitch, src_bytes, v2);
+            load_bytes<16, kWide>(src, at + 3 * pitch, src_bytes, v3);
+            add(v0), add(v1), add(v2), add(v3);
+          }
+          for (; sy < sy1; ++sy, at += pitch) {
+            unsigned v0[4];
+            load_bytes<16, kWide>(src, at, src_bytes, v0);
+            add(v0);
+          }
+        };
+        if (at + (sy1 - 1 - sy0) * pitch + 16 <= src_bytes)
+          rows(std::true_type{});
+        else
+          rows(std::false_type{});
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+          cs[k + 4 * d] = (int)(acc[2 * d] & 0xffffu);
+          cs[k + 4 * d + 1] = (int)(acc[2 * d + 1] & 0xffffu);
+          cs[k + 4 * d + 2] = (int)(acc[2 * d] >> 16);
+          cs[k + 4 * d + 3] = (int)(acc[2 * d + 1] >> 16);
+        }
+      }
+    } else if (any) {
+      const int k = 8 * t;
+      if (k < sx1 - sx0) {
+        int acc[24];
+#pragma unroll
+        for (int j = 0; j < 24; ++j) acc[j] = 0;
+        auto add = [&](int j, int Y, int U, int V) {
+          int r, g, b;
+          yuv_to_rgb(Y, U, V, r, g, b);
+          acc[j] += r, acc[8 + j] += g, acc[16 + j] += b;
+        };
+        if (fmt == ME_PIXFMT_YUYV) {   // rows of Y0 U Y1 V
+          const long long pitch = 2ll * w;
+          long long at = off + sy0 * pitch + 2ll * (sx0 + k);
+          auto rows = [&](auto wide) {
+            for (int sy = sy0; sy < sy1; ++sy, at += pitch) {
+              unsigned v[4];
+              load_bytes<16, decltype(wide)::value>(src, at, src_bytes, v);
+#pragma unroll
+              for (int p = 0; p < 4; ++p) {
+                const int U = (v[p] >> 8) & 255u, V = v[p] >> 24;
+                add(2 * p, v[p] & 255u, U, V);
+                add(2 * p + 1, (v[p] >> 16) & 255u, U, V);
+              }
+            }
+          };
+          if (at + (sy1 - 1 - sy0) * pitch + 16 <= src_bytes)
+            rows(std::true_type{});
+          else
+            rows(std::false_type{});
+        } else {                       // NV12: Y plane [h,w], then the interleaved UV plane [h/2,w]
+          const long long luma = off + (long long)sx0 + k, chroma = luma + (long long)h * w;
+          auto rows = [&](auto wide) {
+            for (int sy = sy0; sy < sy1; ++sy) {
+              unsigned y[2], uv[2];
+              load_bytes<8, decltype(wide)::value>(src, luma + (long long)sy * w, src_bytes, y);
+              load_bytes<8, decltype(wide)::value>(src, chroma + (long long)(sy >> 1) * w, src_bytes, uv);
+#pragma unroll
+              for (int p = 0; p < 4; ++p) {
+                const unsigned c = (uv[p >> 1] >> (16 * (p & 1))) & 0xffffu, yy = (y[p >> 1] >> (16 * (p & 1))) & 0xffffu;
+                add(2 * p, yy & 255u, c & 255u, c >> 8);
+                add(2 * p + 1, yy >> 8, c & 255u, c >> 8);
+              }
+            }
+          };
+          if (chroma + (long long)((sy1 - 1) >> 1) * w + 8 <= src_bytes)   // (the luma plane lies in front of it)
+            rows(std::true_type{});
+          else
+            rows(std::false_type{});
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          cs[k + j] = acc[j];
+          cs[kAreaYuvPix + k + j] = acc[8 + j];
+          cs[2 * kAreaYuvPix + k + j] = acc[16 + j];
+        }
+      }
+    }
+    __syncthreads();
+    // horizontal half: output ox of channel c adds its window's picture columns and divides once; (q, r) of ox P / S is
+    // passed along a run of outputs
+    auto pixel = [&](int c, int& q, int& r) -> float {
+      int q1 = q + qs, r1 = r + rs;   // (ox + 1) P = q1 S + r1
+      if (r1 >= S) r1 -= S, ++q1;
+      const int ax = q, bx = q1 + (r1 > 0);
+      q = q1, r = r1;
+      const int ua = flip ? P - bx : ax, ub = flip ? P - ax : bx;
+      const int xa = ua - pad_left > 0 ? ua - pad_left : 0;
+      const int xb = ub - pad_left < w ? ub - pad_left : w;
+      int sum = 0;
+      if (any) {
+        const int step = yuv ? 1 : 3, first = yuv ? c * kAreaYuvPix : cfirst + cstep * c;
+        for (int x = xa; x < xb; ++x) sum += cs[first + step * (x - sx0)];
+      }
+      return (float)sum / (float)(255 * ((by - ay) * (bx - ax)));
+    };
+    const int nout = ox1 - ox0;
+    if ((S & 3) == 0) {   // ox0 and nout are multiples of 4
+      const int nq = nout >> 2;
+      for (int i = t; i < 3 * nq; i += 256) {
+        const int c = i / nq, ox = ox0 + 4 * (i - c * nq);
+        int q, r;
+        divmod(ox, q, r);
+        float4 v;
+        v.x = pixel(c, q, r);
+        v.y = pixel(c, q, r);
+        v.z = pixel(c, q, r);
+        v.w = pixel(c, q, r);
+        *reinterpret_cast<float4*>(out + (size_t)c * total + ox) = v;
+      }
+    } else {
+      for (int i = t; i < 3 * nout; i += 256) {
+        const int c = i / nout, ox = ox0 + (i - c * nout);
+        int q, r;
+        divmod(ox, q, r);
+        out[(size_t)c * total + ox] = pixel(c, q, r);
+      }
+    }
+    __syncthreads();   // the next segment overwrites cs
+  }
+}
+
 // ---- radar heat map ------------------------------------------------------------------------------------------
 constexpr int HM_MAX = 64;  // max bins per side (radar_maps_size is 32 in the reference)
 
@@ -363,6 +622,19 @@ int me_image_batch_formats_u8_f32(const uint8_t* src, int64_t src_bytes, const i
   hipLaunchKernelGGL(image_batch_formats_kernel, dim3(tiles, n), dim3(256), 0, (hipStream_t)stream, src,
                      (long long)src_bytes, reinterpret_cast<const long long*>(desc), dst, size);
   return me::check_launch("image_batch_formats_kernel");
+}
+
+int me_image_batch_area_u8_f32(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int32_t n, float* dst,
+                               int32_t size, void* stream) {
+  if (n == 0) return 0;
+  ME_REQUIRE(src && desc && dst, ME_E_NULLPTR, "me_image_batch_area_u8_f32: null pointer");
+  ME_REQUIRE(n > 0 && n <= 65535 && size > 0 && src_bytes > 0, ME_E_BADARG,
+             "me_image_batch_area_u8_f32: bad n / size / src_bytes");
+  ME_REQUIRE((long long)size * size < (1ll << 30), ME_E_TOOBIG, "me_image_batch_area_u8_f32: output too large");
+  ME_REQUIRE((size & 3) != 0 || me::aligned16(dst), ME_E_ALIGN, "me_image_batch_area_u8_f32: dst not 16-byte aligned");
+  hipLaunchKernelGGL(image_batch_area_kernel, dim3(size, n), dim3(256), 0, (hipStream_t)stream, src, (long long)src_bytes,
+                     reinterpret_cast<const long long*>(desc), dst, size);
+  return me::check_launch("image_batch_area_kernel");
 }
 
 int me_radar_heatmap_f32(const double* points, const int32_t* offsets, const int32_t* sizes, int32_t n,

@@ -26,7 +26,8 @@ import torch
 
 from . import hip
 from .radar_proposals import DeviceRadarProposals, RadarProposalGenerator
-from .utils.datasets import StagedImages, StagedRadarMaps, StagedRaggedImages, _pad_amounts, picture_hw, pixel_format_names
+from .utils.datasets import (StagedImages, StagedRadarMaps, StagedRaggedImages, _pad_amounts, picture_hw, pixel_format_names,
+                             resize_mode)
 from .utils.utils import box_ops, rescale_boxes, rescale_scalars
 
 __all__ = ["mode_selection", "radar_boxes_for_network", "prepare_streams", "FrameFuser", "MultiStreamFuser"]
@@ -61,15 +62,20 @@ def radar_boxes_for_network(xyxy_pixels, frame_hw):
 
 class FrameFuser:
     """``fuser(frame_uint8_hwc, radar_frames)`` -> ``(detections [m,7], info)``; detections are rows
-    ``(x1, y1, x2, y2, conf, cls_conf, cls_pred)`` in pixels of the original frame, like the demos draw them."""
+    ``(x1, y1, x2, y2, conf, cls_conf, cls_pred)`` in pixels of the original frame, like the demos draw them.
+
+    ``pixel_format``: a name of ``utils.datasets.PIXEL_FORMATS`` - the camera's native frame.  ``resize``: ``None`` /
+    ``"nearest"`` (the reference's resize) or ``"area"`` (``F.interpolate(mode="area")``, an option the reference does not have;
+    semantics and range: ``StagedRaggedImages``).  Either one stages the frame through the ragged-batch kernels."""
 
     def __init__(self, model, calib_param, model_mode=3, img_size=416, nms_iou=0.3, dark_threshold=0.08, generator=None,
-                 pixel_format=None, **generator_kwargs):
+                 pixel_format=None, resize=None, **generator_kwargs):
         self.model, self.model_mode, self.img_size = model, model_mode, img_size
         self.nms_iou, self.dark_threshold = nms_iou, dark_threshold
         # None: uint8 [h,w,3] RGB through the per-frame kernel; a name of utils.datasets.PIXEL_FORMATS: the camera's native
         # frame, staged through the ragged-batch kernel (bit-identical to the per-frame one on the converted frame)
         self.pixel_format = None if pixel_format is None else pixel_format_names(pixel_format, 1)[0]
+        self.resize = resize_mode(resize, "FrameFuser")
         self.generator_is_default = generator is None   # pipeline.py: re-created in the producer vs sent by pickle
         self.generator = generator or RadarProposalGenerator(calib_param, **generator_kwargs)
 
@@ -82,9 +88,9 @@ class FrameFuser:
     def prepare(self, frame, radar_frames):
         """Host half (run_mp.py:65-152 ``pre_process``): a picklable payload for :meth:`infer`."""
         frame = torch.as_tensor(frame)
-        if self.pixel_format is not None:
-            h, w = picture_hw(frame, self.pixel_format)
-            img = StagedRaggedImages([frame], self.img_size, formats=self.pixel_format).pack()
+        if self.pixel_format is not None or self.resize == "area":
+            h, w = picture_hw(frame, self.pixel_format or "rgb")
+            img = StagedRaggedImages([frame], self.img_size, formats=self.pixel_format, resize=self.resize).pack()
         else:
             if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3:
                 raise hip.MeError(f"frame must be uint8 [h,w,3] (got {frame.dtype} {tuple(frame.shape)})")
@@ -113,7 +119,7 @@ class FrameFuser:
                           points=payload["points"])
 
 
-def prepare_streams(frames, radar_frames, streams, img_size=416, pack=False, pixel_format=None):
+def prepare_streams(frames, radar_frames, streams, img_size=416, pack=False, pixel_format=None, resize=None):
     """Host half of a :class:`MultiStreamFuser` step: checks and stages the raw frame bytes and radar frames (picklable; the
     trackers live on the device, so the radar chain itself belongs to ``infer``).  Needs neither a model nor the HIP library:
     ``pipeline.FusionPipeline`` calls it in the producer process with ``pack=True``, which also does the host loop of
@@ -121,20 +127,23 @@ def prepare_streams(frames, radar_frames, streams, img_size=416, pack=False, pix
 
     ``pixel_format``: one name of ``utils.datasets.PIXEL_FORMATS`` or one per stream - the frames are the cameras' native ones
     (``"bgr"`` ``[h,w,3]``, ``"yuyv"`` ``[h,w,2]``, ``"nv12"`` ``[h*3//2, w]``), their bytes are staged as they are and converted
-    on the device; ``payload["hw"]`` is the picture's size.  ``None``: uint8 ``[h,w,3]`` RGB."""
+    on the device; ``payload["hw"]`` is the picture's size.  ``None``: uint8 ``[h,w,3]`` RGB.
+
+    ``resize``: ``None`` / ``"nearest"`` or ``"area"`` (``StagedRaggedImages``); an unknown name raises here."""
+    resize = resize_mode(resize, "prepare_streams")
     if len(frames) != streams or len(radar_frames) != streams:
         raise hip.MeError(f"MultiStreamFuser: {len(frames)} frames / {len(radar_frames)} radar lists for {streams} streams")
     frames = [torch.as_tensor(f) for f in frames]
     if pixel_format is not None:
         names = pixel_format_names(pixel_format, streams, "stream")
         hws = [picture_hw(f, name, f"stream {i}") for i, (f, name) in enumerate(zip(frames, names))]
-        img = StagedRaggedImages(frames, img_size, formats=names)
+        img = StagedRaggedImages(frames, img_size, formats=names, resize=resize)
     else:
         for i, frame in enumerate(frames):
             if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3:
                 raise hip.MeError(f"stream {i}: frame must be uint8 [h,w,3] (got {frame.dtype} {tuple(frame.shape)})")
         hws = [(int(f.shape[0]), int(f.shape[1])) for f in frames]
-        img = StagedRaggedImages(frames, img_size)
+        img = StagedRaggedImages(frames, img_size, resize=resize)
     if pack:
         img.pack(keep_frames=False)
     return dict(hw=hws, img=img, radar_frames=[list(r) for r in radar_frames])
@@ -183,10 +192,18 @@ class MultiStreamFuser:
     ``pixel_format``: one name or one per stream from ``"rgb"``, ``"bgr"``, ``"nv12"``, ``"yuyv"`` - the frames are taken the way
     the camera or the decoder hands them over (:func:`prepare_streams`) and converted by the input kernel
     (``me_image_batch_formats_u8_f32``): no conversion pass on the host, half (NV12) or two thirds (YUYV) of the bytes packed and
-    uploaded, and every stream's rows are ``torch.equal`` to those of its frame converted to RGB.  Default ``None``: RGB."""
+    uploaded, and every stream's rows are ``torch.equal`` to those of its frame converted to RGB.  Default ``None``: RGB.
+
+    ``resize``: ``None`` / ``"nearest"`` - the reference's ``F.interpolate(mode="nearest")``, which keeps one source pixel in
+    ``(P / img_size)^2`` (one in 21 of a 1080p frame at 416) - or ``"area"``: ``F.interpolate(padded_square, img_size,
+    mode="area")``, every source pixel averaged into its output (``me_image_batch_area_u8_f32``, any ``pixel_format``).  The
+    reference's scripts have no such option: ``"area"`` is pinned to torch's float64 ``area`` interpolation rounded to float32,
+    not to the reference.  It needs ``max(h, w) <= 255 * img_size`` per frame, gives the nearest path's bits for ``max(h, w) ==
+    img_size``, and leaves the geometry alone: box rescaling, the radar boxes and the tail do not change, and the auto mode's
+    mean is taken over the area-resized image.  Checked here, when the fuser is built."""
 
     def __init__(self, model, calib_params, streams, model_mode=3, img_size=416, nms_iou=0.3, dark_threshold=0.08,
-                 tail="device", split="forwards", pixel_format=None, **generator_kwargs):
+                 tail="device", split="forwards", pixel_format=None, resize=None, **generator_kwargs):
         self.model, self.model_mode, self.img_size, self.streams = model, model_mode, img_size, int(streams)
         self.nms_iou, self.dark_threshold = nms_iou, dark_threshold
         if tail not in ("device", "host"):
@@ -198,6 +215,7 @@ class MultiStreamFuser:
             raise hip.MeError(f"MultiStreamFuser: streams must be positive (got {streams})")
         # None, one name or one per stream (prepare_streams checks the frames against it)
         self.pixel_format = None if pixel_format is None else pixel_format_names(pixel_format, self.streams, "stream")
+        self.resize = resize_mode(resize, "MultiStreamFuser")
         self.tail = tail
         self.calib_params, self.generator_kwargs = calib_params, generator_kwargs
         self._device = getattr(model, "device", None)
@@ -222,7 +240,8 @@ class MultiStreamFuser:
 
     def prepare(self, frames, radar_frames, pack=False):
         """Host half (:func:`prepare_streams`): a picklable payload for :meth:`infer` / :meth:`advance`."""
-        return prepare_streams(frames, radar_frames, self.streams, self.img_size, pack=pack, pixel_format=self.pixel_format)
+        return prepare_streams(frames, radar_frames, self.streams, self.img_size, pack=pack, pixel_format=self.pixel_format,
+                               resize=self.resize)
 
     def advance(self, payload):
         """The radar chain of one step and nothing else - what :meth:`infer` does first: a step whose detections nobody

@@ -213,6 +213,8 @@ SIGNATURES = {
                                                         C.c_void_p]),
     "me_image_batch_formats_u8_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                                 C.c_void_p]),
+    "me_image_batch_area_u8_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                             C.c_void_p]),
     "me_radar_heatmap_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                        C.c_void_p]),
     "me_radar_capacity": (C.c_int32, [C.c_int32]),

@@ -15,7 +15,8 @@ With a :class:`millieye_amd.demo.MultiStreamFuser` the same two processes carry 
 ``(frames, radar_frames)`` with S entries each; the producer runs the model-free host half (``demo.prepare_streams``: the
 checks and the packing of every frame's bytes into one buffer + descriptor - most of the host time of a step at S = 32) and
 never touches the HIP library or the GPU.  A fuser built with ``pixel_format=`` has the producer pack the cameras' native bytes
-(NV12: half of the RGB bytes, YUYV: two thirds), which is what crosses the process boundary and the PCIe link.  The trackers live on the device, in the consumer, so the producer never drops a
+(NV12: half of the RGB bytes, YUYV: two thirds), which is what crosses the process boundary and the PCIe link; its ``resize=``
+travels with the packed frames.  The trackers live on the device, in the consumer, so the producer never drops a
 step (a dropped step would lose its radar frames and break the tracks): it blocks on the full queue, and the consumer skips
 instead - it takes everything that waits, runs ``advance`` (the radar chain alone) on all but the newest step, in order, and
 ``infer`` on the newest.
@@ -85,30 +86,30 @@ class _MultiPrepareFactory:
     """Picklable recipe of the multi-stream host half: ``demo.prepare_streams`` with the frames packed - no model, no
     generator, no HIP library."""
 
-    def __init__(self, streams, img_size, pixel_format=None):
-        self.streams, self.img_size, self.pixel_format = int(streams), img_size, pixel_format
+    def __init__(self, streams, img_size, pixel_format=None, resize=None):
+        self.streams, self.img_size, self.pixel_format, self.resize = int(streams), img_size, pixel_format, resize
 
     def __call__(self):
         import functools
         from .demo import prepare_streams
         return functools.partial(prepare_streams, streams=self.streams, img_size=self.img_size, pack=True,
-                                 pixel_format=self.pixel_format)
+                                 pixel_format=self.pixel_format, resize=self.resize)
 
 
 class _PrepareFactory:
     """Picklable recipe of the host half: builds a fresh ``FrameFuser`` (without a model) in the producer."""
 
-    def __init__(self, calib_param, img_size, generator_kwargs, generator=None, pixel_format=None):
+    def __init__(self, calib_param, img_size, generator_kwargs, generator=None, pixel_format=None, resize=None):
         self.calib_param, self.img_size, self.generator_kwargs = calib_param, img_size, generator_kwargs
         self.generator = generator   # a caller-supplied generator instance travels by pickle (checked by FusionPipeline)
-        self.pixel_format = pixel_format
+        self.pixel_format, self.resize = pixel_format, resize
 
     def __call__(self):
         from .demo import FrameFuser
         if self.generator is not None:
             return FrameFuser(None, self.calib_param, img_size=self.img_size, generator=self.generator,
-                              pixel_format=self.pixel_format).prepare
-        return FrameFuser(None, self.calib_param, img_size=self.img_size, pixel_format=self.pixel_format,
+                              pixel_format=self.pixel_format, resize=self.resize).prepare
+        return FrameFuser(None, self.calib_param, img_size=self.img_size, pixel_format=self.pixel_format, resize=self.resize,
                           **self.generator_kwargs).prepare
 
 
@@ -138,12 +139,14 @@ class FusionPipeline:
         self.skip_to_newest = skip_to_newest
         self.advance = advance or getattr(fuser, "advance", None)
         if prepare_factory is None and self.multi:
-            prepare_factory = _MultiPrepareFactory(fuser.streams, fuser.img_size, getattr(fuser, "pixel_format", None))
+            prepare_factory = _MultiPrepareFactory(fuser.streams, fuser.img_size, getattr(fuser, "pixel_format", None),
+                                                   getattr(fuser, "resize", None))
         if prepare_factory is None:
             g = fuser.generator
             if getattr(fuser, "generator_is_default", False):
                 prepare_factory = _PrepareFactory(g.calib_param, fuser.img_size, g.kwargs,
-                                                  pixel_format=getattr(fuser, "pixel_format", None))
+                                                  pixel_format=getattr(fuser, "pixel_format", None),
+                                                  resize=getattr(fuser, "resize", None))
             else:
                 try:
                     pickle.dumps(g)
@@ -151,7 +154,8 @@ class FusionPipeline:
                     raise TypeError("FusionPipeline: the FrameFuser was built with a custom generator= that cannot be "
                                     f"pickled into the producer process ({exc}); pass prepare_factory= instead") from exc
                 prepare_factory = _PrepareFactory(getattr(g, "calib_param", None), fuser.img_size, {}, generator=g,
-                                                  pixel_format=getattr(fuser, "pixel_format", None))
+                                                  pixel_format=getattr(fuser, "pixel_format", None),
+                                                  resize=getattr(fuser, "resize", None))
         self.prepare_factory = prepare_factory
         self.ctx = mp.get_context(start_method)      # run_mp.py:287: spawn
         self.stats = {}

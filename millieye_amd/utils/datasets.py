@@ -28,7 +28,7 @@ from torch.utils.data import Dataset
 from .. import hip
 
 __all__ = ["MyDataset", "StagedImages", "StagedRaggedImages", "StagedRadarMaps", "obtain_bboxs", "PIXEL_FORMATS",
-           "picture_hw"]
+           "picture_hw", "RESIZE_MODES", "resize_mode"]
 
 _SCENES = ["0", "1", "2", "3", "4"]
 
@@ -160,6 +160,16 @@ def picture_hw(frame, pixel_format="rgb", what="frame"):
     return int(hw[0]), int(hw[1])
 
 
+RESIZE_MODES = ("nearest", "area")
+
+
+def resize_mode(resize, what="resize"):
+    """``None`` or one checked name of :data:`RESIZE_MODES`."""
+    if resize is not None and (not isinstance(resize, str) or resize not in RESIZE_MODES):
+        raise hip.MeError(f"{what}: unknown resize mode {resize!r} (one of {', '.join(RESIZE_MODES)})")
+    return resize
+
+
 class StagedRaggedImages(StagedImages):
     """A ``StagedImages`` whose ``.to(device)`` builds the whole batch in one launch: every frame's bytes are packed into one
     pinned uint8 buffer and uploaded once, with a ``[n,4]`` int64 descriptor ``(byte offset, h, w, flip)`` per frame, and
@@ -169,23 +179,38 @@ class StagedRaggedImages(StagedImages):
     ``formats``: one name of :data:`PIXEL_FORMATS` or one per frame - the frames are what a camera or a decoder hands over
     (shapes: :func:`picture_hw`), their native bytes are packed, the descriptor is ``[n,5]`` ``(byte offset, h, w, flip,
     format id)`` with the picture's ``h, w``, and ``me_image_batch_formats_u8_f32`` converts on the device: a frame gives the
-    bits its RGB conversion gives on the default path.  ``formats=None`` is the default path."""
+    bits its RGB conversion gives on the default path.  ``formats=None`` is the default path.
+
+    ``resize``: a name of :data:`RESIZE_MODES`.  ``None`` / ``"nearest"``: the reference's ``F.interpolate(mode="nearest")``,
+    everything above as it is.  ``"area"``: ``F.interpolate(padded_square, size, mode="area")`` - every source pixel is
+    averaged into the output instead of one in ``(P / size)^2`` being kept - by ``me_image_batch_area_u8_f32``, always with the
+    ``[n,5]`` descriptor (``formats=None``: all RGB).  The reference's scripts have no such option; the result is pinned to
+    torch's float64 ``area`` interpolation of the padded ``u8 / 255`` square rounded to float32, which the kernel's integer
+    arithmetic gives exactly (include/millieye_hip.h).  It needs ``max(h, w) <= 255 * size`` per frame (``pack()`` raises
+    otherwise); with ``max(h, w) == size`` it gives the bits of the nearest path, and the geometry is the same, so box
+    rescaling does not change."""
 
     packed = desc = None   # set by pack(): the frames' bytes in one uint8 buffer and the [n,4] ([n,5]) int64 descriptor
     formats = None         # None: packed RGB and the [n,4] descriptor; else one checked name per frame
+    resize = None          # None / "nearest": the nearest kernels; "area": me_image_batch_area_u8_f32
 
-    def __init__(self, frames, size, flips=None, formats=None):
+    def __init__(self, frames, size, flips=None, formats=None, resize=None):
         super().__init__(frames, size, flips)
+        self.resize = resize_mode(resize, "StagedRaggedImages")
         if formats is not None:
             self.formats = pixel_format_names(formats, len(self.frames))
+        if formats is not None or self.resize == "area":
             self.frames = [torch.as_tensor(f) for f in self.frames]
 
     def _format_descriptor(self):
         """The ``[n,5]`` descriptor of the native frames and their byte total; checks every frame (:func:`picture_hw`)."""
         desc = torch.empty((len(self.frames), 5), dtype=torch.int64)
         total = 0
-        for i, (frame, name) in enumerate(zip(self.frames, self.formats)):
+        for i, (frame, name) in enumerate(zip(self.frames, self.formats or ["rgb"] * len(self.frames))):
             h, w = picture_hw(frame, name, f"frame {i}")
+            if self.resize == "area" and max(h, w) > 255 * self.size:
+                raise hip.MeError(f"frame {i}: {h} x {w} is beyond the area resize's range max(h, w) <= 255 * size = "
+                                  f"{255 * self.size}")
             desc[i] = torch.tensor([total, h, w, int(self.flips[i]), PIXEL_FORMATS[name]])
             total += frame.numel()
         return desc, total
@@ -195,7 +220,7 @@ class StagedRaggedImages(StagedImages):
         their bytes into one buffer.  The object then carries ``packed`` / ``desc`` (through pickle too) and :meth:`to` only
         uploads them; ``keep_frames=False`` drops the per-frame tensors so that the bytes travel once."""
         n = len(self.frames)
-        if self.formats is not None:
+        if self.formats is not None or self.resize == "area":
             desc, total = self._format_descriptor()
         else:
             desc = torch.empty((n, 4), dtype=torch.int64)
@@ -226,12 +251,16 @@ class StagedRaggedImages(StagedImages):
         out = torch.empty(tuple(self.shape), device=device, dtype=torch.float32)
         if n == 0:
             return out
-        src = self if self.packed is not None else StagedRaggedImages(self.frames, self.size, self.flips,
-                                                                      self.formats).pack(pin=True)
+        src = self if self.packed is not None else StagedRaggedImages(self.frames, self.size, self.flips, self.formats,
+                                                                      self.resize).pack(pin=True)
         packed, desc = src.packed, src.desc
         total = int(packed.numel())
         d_src = packed.to(device, non_blocking=True)
         d_desc = desc.pin_memory().to(device, non_blocking=True)
+        if self.resize == "area":
+            hip.check(hip.lib().me_image_batch_area_u8_f32(d_src.data_ptr(), total, d_desc.data_ptr(), n, out.data_ptr(),
+                                                           self.size, hip.stream_ptr()), "me_image_batch_area_u8_f32")
+            return out
         if self.formats is not None:
             hip.check(hip.lib().me_image_batch_formats_u8_f32(d_src.data_ptr(), total, d_desc.data_ptr(), n, out.data_ptr(),
                                                               self.size, hip.stream_ptr()), "me_image_batch_formats_u8_f32")

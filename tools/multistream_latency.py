@@ -23,7 +23,12 @@ python tools/multistream_latency.py --split compare --streams 8 32 --steps 40 --
 ``--pixel-format rgb nv12 yuyv`` prints only the comparison of the input formats (:func:`compare_formats`;
 profiles/multistream_pixel_formats.txt): per network and S the bytes a step packs, the time from the packed payload to the device
 batch, the whole in-process step and the two-process pipeline, every format in the same process, in blocks whose order rotates:
-python tools/multistream_latency.py --pixel-format rgb nv12 yuyv --streams 8 32 --steps 40 --out profiles/multistream_pixel_formats.txt"""
+python tools/multistream_latency.py --pixel-format rgb nv12 yuyv --streams 8 32 --steps 40 --out profiles/multistream_pixel_formats.txt
+
+``--resize nearest area`` prints only the comparison of the resize modes (:func:`compare_resize`; profiles/multistream_resize.txt):
+per network, S, frame size (``--frame-size H W``, repeatable) and pixel format the bytes a step packs, the input launch's own time,
+a device-to-device copy of the same packed buffer, the area launch's source-read rate as a fraction of that copy's, and the step:
+python tools/multistream_latency.py --resize nearest area --frame-size 480 640 --frame-size 1080 1920 --streams 8 32 --steps 20 --out profiles/multistream_resize.txt"""
 import argparse
 import os
 import statistics
@@ -160,6 +165,92 @@ def compare_formats(args, say):
                 say(line)
 
 
+def compare_resize(args, say):
+    """``--resize``: the resize modes of ``MultiStreamFuser(resize=)`` against the first one named (nearest) in one process, in
+    rotating blocks like :func:`compare_formats`.  Per network, S, frame size (``--frame-size``, repeatable) and pixel format
+    (``--pixel-format``, default rgb nv12), every mode's fuser sees the same dark frames and radar streams.
+
+    bytes/step: what ``prepare(pack=True)`` packs.  "launch": the input launch alone on buffers that are already on the device -
+    HIP events around a block of back-to-back launches, divided by their number; the sources rotate over a ring of copies of the
+    packed buffer of about 1 GB (at most 16), so that a launch does not find its source in the Infinity Cache where the ring is
+    larger than it.  "copy": ``copy_`` of the same packed buffers device to device over the same ring, the same way; "of copy" is
+    copy time / launch time of the area mode = its source-read rate as a fraction of the copy's rate (the copy also writes what
+    it reads; the area launch writes ``S x 3 x 416 x 416`` floats).  "step": the whole in-process step from the caller's frames."""
+    from millieye_amd import hip
+    modes = args.resize
+    fmts = args.pixel_format or ["rgb", "nv12"]
+    sizes = [tuple(v) for v in (args.frame_size or [[480, 640]])]
+    say(f"# {torch.cuda.get_device_name(0)}; dark frames; {args.steps} steps (launches, copies) per block, {args.repeats} blocks per "
+        f"mode in rotating order, median (min .. max) of the blocks, 5 warm-up steps")
+    entry = {"nearest": "me_image_batch_formats_u8_f32", "area": "me_image_batch_area_u8_f32"}
+    for cfg, dtype in args.nets:
+        net = _demo_net(cfg, dtype)
+        for n in args.streams:
+            radar = [[[radar_points((f + 7 * s) % 45)] for s in range(n)] for f in range(args.steps)]
+            for h, w in sizes:
+                for fmt in fmts:
+                    distinct = [dark_native_frame(fmt, s, h, w) for s in range(min(n, 4))]   # (four pictures, in turn)
+                    frames = [distinct[s % len(distinct)] for s in range(n)]
+                    fusers = {m: MultiStreamFuser(net, RADAR_CALIB, n, model_mode=3, min_hits=2, pixel_format=fmt, resize=m)
+                              for m in modes}
+                    payload = fusers[modes[0]].prepare(frames, radar[0], pack=True)
+                    packed, desc = payload["img"].packed, payload["img"].desc
+                    nbytes = int(packed.numel())
+                    dev = fusers[modes[0]].device
+                    ring = [packed.to(dev) for _ in range(max(1, min(16, -(-(1 << 30) // nbytes))))]
+                    spare = torch.empty_like(ring[0])
+                    d_desc = desc.to(dev)
+                    out = torch.empty((n, 3, 416, 416), device=dev, dtype=torch.float32)
+                    lib, stream = hip.lib(), hip.stream_ptr()
+
+                    def launches(mode):
+                        fn = getattr(lib, entry[mode])
+                        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        torch.cuda.synchronize()
+                        a.record()
+                        for f in range(args.steps):
+                            hip.check(fn(ring[f % len(ring)].data_ptr(), nbytes, d_desc.data_ptr(), n, out.data_ptr(), 416, stream),
+                                      entry[mode])
+                        b.record()
+                        torch.cuda.synchronize()
+                        return a.elapsed_time(b) * 1e-3 / args.steps
+
+                    def copies(_mode):
+                        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        torch.cuda.synchronize()
+                        a.record()
+                        for f in range(args.steps):
+                            spare.copy_(ring[f % len(ring)])
+                        b.record()
+                        torch.cuda.synchronize()
+                        return a.elapsed_time(b) * 1e-3 / args.steps
+
+                    for f in range(5):
+                        for m in modes:
+                            res = fusers[m](frames, radar[f])
+                    assert all(info["mode"] == 0 for _r, info in res)
+                    variants = [("launch", m) for m in modes] + [("copy", None)]
+                    for kind, m in variants:
+                        (launches if kind == "launch" else copies)(m)
+                    t_dev = [[] for _ in variants]
+                    for r in range(args.repeats):
+                        for i in [(r + j) % len(variants) for j in range(len(variants))]:
+                            kind, m = variants[i]
+                            t_dev[i].append((launches if kind == "launch" else copies)(m))
+                    t_step = timed_rotating([lambda f, m=m: fusers[m](frames, radar[f]) for m in modes], args.steps, args.repeats)
+                    t_copy = statistics.median(t_dev[-1])
+                    for i, m in enumerate(modes):
+                        t_launch = statistics.median(t_dev[i])
+                        line = (f"{cfg:16s} {dtype:4s} S={n:2d} {h}x{w} {fmt:4s} {m:7s}: {nbytes / 1e6:7.2f} MB/step, ring of {len(ring):2d} | "
+                                f"launch {_spread(t_dev[i], 1e6)} us | copy {_spread(t_dev[-1], 1e6)} us")
+                        if m == "area":
+                            line += f" | source read {nbytes / t_launch / 1e9:7.1f} GB/s = {t_copy / t_launch:4.2f} of copy"
+                        line += (f" | step {_spread(t_step[i])} ms "
+                                 f"({(statistics.median(t_step[i]) / statistics.median(t_step[0]) - 1) * 100:+6.1f} %)")
+                        say(line)
+                    del ring, spare, out
+
+
 def timed_ab(fn_a, fn_b, steps, repeats=4):
     """``timed`` for two variants, a block of each per repeat in alternating order (A B, B A, ...), so that both see the same
     machine state and neither always runs first."""
@@ -266,9 +357,14 @@ def main():
     ap.add_argument("--vary-steps", type=int, default=36, help="--split compare: steps of the run with a changing dark count")
     ap.add_argument("--pixel-format", nargs="+", default=None, choices=["rgb", "bgr", "nv12", "yuyv"],
                     help="only the comparison of these input formats against the first one (compare_formats)")
-    ap.add_argument("--repeats", type=int, default=4, help="--pixel-format: blocks per format")
+    ap.add_argument("--repeats", type=int, default=4, help="--pixel-format / --resize: blocks per variant")
     ap.add_argument("--nets", nargs="*", default=["yolov3-tiny-12:f32", "yolov3:bf16"],
-                    help="--pixel-format: the cfg:dtype pairs to measure")
+                    help="--pixel-format / --resize: the cfg:dtype pairs to measure")
+    ap.add_argument("--resize", nargs="+", default=None, choices=["nearest", "area"],
+                    help="only the comparison of these resize modes against the first one (compare_resize), for the formats of "
+                         "--pixel-format (default rgb nv12)")
+    ap.add_argument("--frame-size", nargs=2, type=int, action="append", metavar=("H", "W"), default=None,
+                    help="--resize: the frames' size (default 480 640); may be given several times")
     args = ap.parse_args()
     args.nets = [tuple(v.split(":")) for v in args.nets]
     lines = []
@@ -278,6 +374,12 @@ def main():
         lines.append(text)
 
     say(f"# python tools/multistream_latency.py {' '.join(sys.argv[1:])}".rstrip())
+    if args.resize:
+        compare_resize(args, say)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return
     if args.pixel_format:
         compare_formats(args, say)
         if args.out:
