@@ -162,6 +162,22 @@ typedef struct me_yolo_desc {
   float anchors[16];
 } me_yolo_desc;
 int me_yolo_decode_f32(const me_yolo_desc* d, void* stream);
+/* me_yolo_decode_rect_f32 - the same decode on a rectangular grid (no reference counterpart: the reference's YOLOLayer views
+ * its map as [.., grid_size, grid_size] and cannot run one; the rule is Darknet's own): x NHWC [n,gh,gw,A*(5+C)],
+ *   out row r = row_offset + a*gh*gw + gy*gw + gx, k=0 uses gx, k=1 uses gy, one `stride` = H/gh = W/gw for both axes, the same
+ *   float32 operations in the same order.  me_yolo_rect_desc is me_yolo_desc with (gh, gw) in the place of g (same size, not
+ *   the same layout); with gh == gw every row equals me_yolo_decode_f32's bit for bit.  The square entry points run the same
+ *   kernels with gh = gw = g. */
+typedef struct me_yolo_rect_desc {
+  const float* x;
+  float* out;
+  int64_t x_pitch;
+  int32_t n, gh, gw, num_anchors, num_classes;
+  int32_t rows_total, row_offset;
+  float stride;
+  float anchors[16];
+} me_yolo_rect_desc;
+int me_yolo_decode_rect_f32(const me_yolo_rect_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * me_nms_batched_f32 - confidence filter + class-aware greedy NMS, per image.
@@ -198,6 +214,11 @@ int me_yolo_decode_cand_f32(const me_yolo_desc* y, float conf_thresh, void* nms_
  * the last head convolution has run); the scales share n, rows_total and out. */
 int me_yolo_decode_cand_multi_f32(const me_yolo_desc* const* ys, int32_t count, float conf_thresh, void* nms_workspace,
                                   int32_t first, void* stream);
+/* the two candidate-list decodes on rectangular grids (me_yolo_rect_desc; same checks plus gh, gw > 0, same workspace, same
+ * identity: me_yolo_decode_cand[_multi]_rect_f32 + me_nms_batched_prepped_f32 == me_yolo_decode_rect_f32 + me_nms_batched_f32) */
+int me_yolo_decode_cand_rect_f32(const me_yolo_rect_desc* y, float conf_thresh, void* nms_workspace, int32_t first, void* stream);
+int me_yolo_decode_cand_multi_rect_f32(const me_yolo_rect_desc* const* ys, int32_t count, float conf_thresh, void* nms_workspace,
+                                       int32_t first, void* stream);
 int me_nms_batched_prepped_f32(const me_nms_desc* d, void* stream);
 /* me_nms_candidate_counts: after me_nms_batched_f32 / me_nms_batched_prepped_f32 (or the decodes that fill the lists) on
  * `workspace` for [n, rows] predictions, cand_count[n] <- the number of rows of image i with objectness >= conf_thresh (the
@@ -947,7 +968,7 @@ int me_adam_step_f32(const me_adam_desc* d, void* stream);
 int32_t me_adam_chunk(void);
 
 /* sizes of the descriptor structs, so a binding can assert its mirror layout */
-int32_t me_sizeof(int32_t which); /* 0 conv, 1 pool, 2 yolo, 3 nms, 4 heads, 5 heads_weights, 6 conv16, 7 pack, 8 bneck16, 9 adam, 10 radar, 11 nms_python */
+int32_t me_sizeof(int32_t which); /* 0 conv, 1 pool, 2 yolo, 3 nms, 4 heads, 5 heads_weights, 6 conv16, 7 pack, 8 bneck16, 9 adam, 10 radar, 11 nms_python, 12 yolo_rect */
 
 #ifdef __cplusplus
 }

@@ -68,6 +68,23 @@ __device__ __forceinline__ void store4(float* ptr, float v, int mode) {
     __builtin_nontemporal_store(v, ptr);
 }
 
+// the decode kernels' parameter block of a square descriptor: gh = gw = g
+inline me_yolo_rect_desc yolo_rect_of(const me_yolo_desc& s) {
+  me_yolo_rect_desc r;
+  r.x = s.x;
+  r.out = s.out;
+  r.x_pitch = s.x_pitch;
+  r.n = s.n;
+  r.gh = r.gw = s.g;
+  r.num_anchors = s.num_anchors;
+  r.num_classes = s.num_classes;
+  r.rows_total = s.rows_total;
+  r.row_offset = s.row_offset;
+  r.stride = s.stride;
+  for (int i = 0; i < 16; ++i) r.anchors[i] = s.anchors[i];
+  return r;
+}
+
 }  // namespace me
 
 #define ME_REQUIRE(cond, code, ...)   \

@@ -134,11 +134,13 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float* x, long 
 
 // ---- YOLO decode -------------------------------------------------------------------------------
 // one thread per output element (n, a, pixel, k): reads and writes are both contiguous in k.
-__global__ __launch_bounds__(kThreads) void yolo_decode_kernel(me_yolo_desc d) {
-  // blockIdx.y = (image, anchor); blockIdx.x strides over that anchor's g*g*(5+C) elements: one 32-bit division per
+// The parameter block is the rectangular descriptor: me_yolo_decode_f32 fills gh = gw = g (square launches compute what they
+// computed with one g: the same integers, the same float operations).
+__global__ __launch_bounds__(kThreads) void yolo_decode_kernel(me_yolo_rect_desc d) {
+  // blockIdx.y = (image, anchor); blockIdx.x strides over that anchor's gh*gw*(5+C) elements: one 32-bit division per
   // element (the flat 64-bit index needed three), reads and writes contiguous in k
   const unsigned per = d.num_classes + 5;
-  const unsigned gg = d.g * d.g;
+  const unsigned gg = d.gh * d.gw;
   const unsigned a = blockIdx.y % d.num_anchors, nimg = blockIdx.y / d.num_anchors;
   const unsigned total = gg * per;
   const float* xin = d.x + (long long)nimg * gg * d.x_pitch + a * per;
@@ -151,7 +153,7 @@ __global__ __launch_bounds__(kThreads) void yolo_decode_kernel(me_yolo_desc d) {
     float o;
     if (k < 2) {
       const float s = 1.f / (1.f + expf(-v));
-      const float g = (k == 0) ? (float)(pix % d.g) : (float)(pix / d.g);
+      const float g = (k == 0) ? (float)(pix % d.gw) : (float)(pix / d.gw);  // pix = gy * gw + gx
       o = (s + g) * d.stride;
     } else if (k < 4) {
       // reference order: exp(t) * (anchor / stride), then * stride (yolov3/models.py:126,162-163,168)
@@ -251,23 +253,35 @@ int me_nhwc_to_nchw_f32(const float* x, int64_t x_pitch, float* y, int32_t n, in
   return me::check_launch("nhwc_to_nchw_kernel");
 }
 
-int me_yolo_decode_f32(const me_yolo_desc* d, void* stream_) {
+// both decode entry points: `what` names the caller in the messages
+static int yolo_decode(const me_yolo_rect_desc* d, void* stream_, const char* what) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  ME_REQUIRE(d && d->x && d->out, ME_E_NULLPTR, "me_yolo_decode_f32: null pointer");
-  ME_REQUIRE(d->n > 0 && d->g > 0 && d->num_anchors > 0 && d->num_anchors <= 8 && d->num_classes >= 0, ME_E_BADARG,
-             "me_yolo_decode_f32: bad dimensions");
-  ME_REQUIRE(d->x_pitch >= d->num_anchors * (d->num_classes + 5), ME_E_BADARG, "me_yolo_decode_f32: x_pitch too small");
-  ME_REQUIRE(d->row_offset >= 0 && d->row_offset + d->num_anchors * d->g * d->g <= d->rows_total, ME_E_BADARG,
-             "me_yolo_decode_f32: rows out of range");
-  ME_REQUIRE(d->stride > 0.f, ME_E_BADARG, "me_yolo_decode_f32: stride must be positive");
-  const long long per_anchor = (long long)d->g * d->g * (d->num_classes + 5);
-  ME_REQUIRE(per_anchor < (1ll << 31) && (long long)d->n * d->num_anchors < 65536, ME_E_TOOBIG,
-             "me_yolo_decode_f32: grid too large");
+  ME_REQUIRE(d->x && d->out, ME_E_NULLPTR, "%s: null pointer", what);
+  ME_REQUIRE(d->n > 0 && d->gh > 0 && d->gw > 0 && d->num_anchors > 0 && d->num_anchors <= 8 && d->num_classes >= 0,
+             ME_E_BADARG, "%s: bad dimensions", what);
+  ME_REQUIRE(d->x_pitch >= d->num_anchors * (d->num_classes + 5), ME_E_BADARG, "%s: x_pitch too small", what);
+  const long long cells = (long long)d->gh * d->gw;
+  ME_REQUIRE(d->row_offset >= 0 && d->row_offset + d->num_anchors * cells <= d->rows_total, ME_E_BADARG,
+             "%s: rows out of range", what);
+  ME_REQUIRE(d->stride > 0.f, ME_E_BADARG, "%s: stride must be positive", what);
+  const long long per_anchor = cells * (d->num_classes + 5);
+  ME_REQUIRE(per_anchor < (1ll << 31) && (long long)d->n * d->num_anchors < 65536, ME_E_TOOBIG, "%s: grid too large", what);
   long long bx = (per_anchor + kThreads - 1) / kThreads;
   if (bx > 64) bx = 64;
   hipLaunchKernelGGL(yolo_decode_kernel, dim3((unsigned)bx, (unsigned)(d->n * d->num_anchors)), dim3(kThreads), 0, stream,
                      *d);
   return me::check_launch("yolo_decode_kernel");
+}
+
+int me_yolo_decode_f32(const me_yolo_desc* d, void* stream) {
+  ME_REQUIRE(d, ME_E_NULLPTR, "me_yolo_decode_f32: null pointer");
+  const me_yolo_rect_desc r = me::yolo_rect_of(*d);
+  return yolo_decode(&r, stream, "me_yolo_decode_f32");
+}
+
+int me_yolo_decode_rect_f32(const me_yolo_rect_desc* d, void* stream) {
+  ME_REQUIRE(d, ME_E_NULLPTR, "me_yolo_decode_rect_f32: null pointer");
+  return yolo_decode(d, stream, "me_yolo_decode_rect_f32");
 }
 
 }  // extern "C"

@@ -236,7 +236,7 @@ __global__ __launch_bounds__(256) void nms_prep_kernel(float* pred, int rows, in
 // decode that wrote it (78 - 100 us at batch 32, the largest part of the NMS stage after round 3's select rewrite).
 // One wave per row (5 + C <= 128 elements: lane k and k + 64), 64 rows per workgroup, one global atomic per workgroup.
 struct YoloCand {
-  me_yolo_desc y[3];  // the [yolo] scales of one launch (count of them used)
+  me_yolo_rect_desc y[3];  // the [yolo] scales of one launch (count of them used); the square entry points fill gh = gw = g
   int wg_end[3];      // exclusive prefix sums of the workgroups per scale
   int count;
   float conf_thresh;
@@ -273,11 +273,11 @@ __global__ __launch_bounds__(256) void yolo_decode_cand_kernel(YoloCand d, NmsWs
   int sc = 0, bx = blockIdx.x;
   if (d.count > 1 && bx >= d.wg_end[0]) sc = (d.count > 2 && bx >= d.wg_end[1]) ? 2 : 1;
   if (sc) bx -= d.wg_end[sc - 1];
-  const me_yolo_desc& y = d.y[sc];
+  const me_yolo_rect_desc& y = d.y[sc];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int img = blockIdx.y;
   const int per = y.num_classes + 5;
-  const int gg = y.g * y.g;
+  const int gg = y.gh * y.gw;
   const int rows_scale = y.num_anchors * gg;
   if (threadIdx.x == 0) {
     s_n = 0;
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(256) void yolo_decode_cand_kernel(YoloCand d, NmsWs
     const int row = y.row_offset + rr;  // row of the prediction tensor
     float* out = y.out + ((long long)img * y.rows_total + row) * per;
     const float aw = y.anchors[2 * a], ah = y.anchors[2 * a + 1];
-    const float gx = (float)(pix % y.g), gy = (float)(pix / y.g);
+    const float gx = (float)(pix % y.gw), gy = (float)(pix / y.gw);  // pix = gy * gw + gx
     float v[2] = {0.f, 0.f};
     // the kernel is VALU-bound (one wave per row of 85 values): ONE expf per element - of t for the w / h lanes, of -t for the
     // sigmoid lanes - instead of the three divergent paths; every element still sees the reference's operations in their order
@@ -1301,28 +1301,28 @@ int me_nms_batched_f32(const me_nms_desc* d, void* stream) { return nms_batched(
 /* the candidate lists are already in the workspace (me_yolo_decode_cand_f32 of every scale): select + emit only */
 int me_nms_batched_prepped_f32(const me_nms_desc* d, void* stream) { return nms_batched(d, stream, 1); }
 
-int me_yolo_decode_cand_multi_f32(const me_yolo_desc* const* ys, int32_t count, float conf_thresh, void* nms_workspace,
-                                  int32_t first, void* stream_) {
+// the candidate-list decode of `count` scales (square entry points: converted with gh = gw = g); `what` names the caller
+static int yolo_decode_cand(const me_yolo_rect_desc* ys, int32_t count, float conf_thresh, void* nms_workspace, int32_t first,
+                            void* stream_, const char* what) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  ME_REQUIRE(ys && nms_workspace, ME_E_NULLPTR, "me_yolo_decode_cand_f32: null pointer");
-  ME_REQUIRE(count >= 1 && count <= 3, ME_E_BADARG, "me_yolo_decode_cand_f32: 1 - 3 scales per launch (got %d)", count);
-  ME_REQUIRE((reinterpret_cast<uintptr_t>(nms_workspace) & 255u) == 0, ME_E_ALIGN, "me_yolo_decode_cand_f32: workspace alignment");
+  ME_REQUIRE((reinterpret_cast<uintptr_t>(nms_workspace) & 255u) == 0, ME_E_ALIGN, "%s: workspace alignment", what);
   long long rows_all = 0;
   for (int i = 0; i < count; ++i) {
-    const me_yolo_desc* y = ys[i];
-    ME_REQUIRE(y && y->x && y->out, ME_E_NULLPTR, "me_yolo_decode_cand_f32: null pointer");
-    ME_REQUIRE(y->n > 0 && y->g > 0 && y->num_anchors > 0 && y->num_anchors <= 8 && y->num_classes >= 0 &&
-                   y->num_classes + 5 <= 128, ME_E_BADARG, "me_yolo_decode_cand_f32: bad dimensions (5 + classes <= 128)");
-    ME_REQUIRE(y->x_pitch >= y->num_anchors * (y->num_classes + 5), ME_E_BADARG, "me_yolo_decode_cand_f32: x_pitch too small");
-    ME_REQUIRE(y->row_offset >= 0 && y->row_offset + y->num_anchors * y->g * y->g <= y->rows_total && y->rows_total <= MAX_ROWS,
-               ME_E_BADARG, "me_yolo_decode_cand_f32: rows out of range");
-    ME_REQUIRE(y->n <= 65535 && y->stride > 0.f, ME_E_BADARG, "me_yolo_decode_cand_f32: bad batch / stride");
-    ME_REQUIRE(y->n == ys[0]->n && y->rows_total == ys[0]->rows_total && y->out == ys[0]->out, ME_E_BADARG,
-               "me_yolo_decode_cand_f32: the scales of one launch share the batch and the prediction tensor");
-    rows_all += (long long)y->num_anchors * y->g * y->g;
+    const me_yolo_rect_desc* y = &ys[i];
+    ME_REQUIRE(y->x && y->out, ME_E_NULLPTR, "%s: null pointer", what);
+    ME_REQUIRE(y->n > 0 && y->gh > 0 && y->gw > 0 && y->num_anchors > 0 && y->num_anchors <= 8 && y->num_classes >= 0 &&
+                   y->num_classes + 5 <= 128, ME_E_BADARG, "%s: bad dimensions (5 + classes <= 128)", what);
+    ME_REQUIRE(y->x_pitch >= y->num_anchors * (y->num_classes + 5), ME_E_BADARG, "%s: x_pitch too small", what);
+    const long long rows_scale = (long long)y->num_anchors * y->gh * y->gw;
+    ME_REQUIRE(y->row_offset >= 0 && y->row_offset + rows_scale <= y->rows_total && y->rows_total <= MAX_ROWS, ME_E_BADARG,
+               "%s: rows out of range", what);
+    ME_REQUIRE(y->n <= 65535 && y->stride > 0.f, ME_E_BADARG, "%s: bad batch / stride", what);
+    ME_REQUIRE(y->n == ys[0].n && y->rows_total == ys[0].rows_total && y->out == ys[0].out, ME_E_BADARG,
+               "%s: the scales of one launch share the batch and the prediction tensor", what);
+    rows_all += rows_scale;
   }
-  const int n = ys[0]->n;
-  NmsWs w = carve(nms_workspace, n, ys[0]->rows_total);
+  const int n = ys[0].n;
+  NmsWs w = carve(nms_workspace, n, ys[0].rows_total);
   if (first) {
     // a kernel, not hipMemsetAsync: this launch sequence is captured into hipGraphs (engine._run_graph), and on this ROCm (7.2) a
     // captured hipMemsetAsync of 64 bytes or more clears the words on the FIRST replay only - later replays write a pointer-like
@@ -1340,8 +1340,8 @@ int me_yolo_decode_cand_multi_f32(const me_yolo_desc* const* ys, int32_t count, 
   d.conf_thresh = conf_thresh;
   int wgs = 0;
   for (int i = 0; i < 3; ++i) {
-    d.y[i] = *ys[i < count ? i : 0];
-    if (i < count) wgs += (ys[i]->num_anchors * ys[i]->g * ys[i]->g + 4 * rpw - 1) / (4 * rpw);
+    d.y[i] = ys[i < count ? i : 0];
+    if (i < count) wgs += (ys[i].num_anchors * ys[i].gh * ys[i].gw + 4 * rpw - 1) / (4 * rpw);
     d.wg_end[i] = wgs;
   }
   const dim3 grid(wgs, n), block(256);
@@ -1351,8 +1351,37 @@ int me_yolo_decode_cand_multi_f32(const me_yolo_desc* const* ys, int32_t count, 
   return me::check_launch("yolo_decode_cand_kernel");
 }
 
+int me_yolo_decode_cand_multi_f32(const me_yolo_desc* const* ys, int32_t count, float conf_thresh, void* nms_workspace,
+                                  int32_t first, void* stream) {
+  ME_REQUIRE(ys && nms_workspace, ME_E_NULLPTR, "me_yolo_decode_cand_f32: null pointer");
+  ME_REQUIRE(count >= 1 && count <= 3, ME_E_BADARG, "me_yolo_decode_cand_f32: 1 - 3 scales per launch (got %d)", count);
+  me_yolo_rect_desc r[3];
+  for (int i = 0; i < count; ++i) {
+    ME_REQUIRE(ys[i], ME_E_NULLPTR, "me_yolo_decode_cand_f32: null pointer");
+    r[i] = me::yolo_rect_of(*ys[i]);
+  }
+  return yolo_decode_cand(r, count, conf_thresh, nms_workspace, first, stream, "me_yolo_decode_cand_f32");
+}
+
 int me_yolo_decode_cand_f32(const me_yolo_desc* y, float conf_thresh, void* nms_workspace, int32_t first, void* stream) {
   return me_yolo_decode_cand_multi_f32(&y, 1, conf_thresh, nms_workspace, first, stream);
+}
+
+int me_yolo_decode_cand_multi_rect_f32(const me_yolo_rect_desc* const* ys, int32_t count, float conf_thresh, void* nms_workspace,
+                                       int32_t first, void* stream) {
+  ME_REQUIRE(ys && nms_workspace, ME_E_NULLPTR, "me_yolo_decode_cand_rect_f32: null pointer");
+  ME_REQUIRE(count >= 1 && count <= 3, ME_E_BADARG, "me_yolo_decode_cand_rect_f32: 1 - 3 scales per launch (got %d)", count);
+  me_yolo_rect_desc r[3];
+  for (int i = 0; i < count; ++i) {
+    ME_REQUIRE(ys[i], ME_E_NULLPTR, "me_yolo_decode_cand_rect_f32: null pointer");
+    r[i] = *ys[i];
+  }
+  return yolo_decode_cand(r, count, conf_thresh, nms_workspace, first, stream, "me_yolo_decode_cand_rect_f32");
+}
+
+int me_yolo_decode_cand_rect_f32(const me_yolo_rect_desc* y, float conf_thresh, void* nms_workspace, int32_t first,
+                                 void* stream) {
+  return me_yolo_decode_cand_multi_rect_f32(&y, 1, conf_thresh, nms_workspace, first, stream);
 }
 
 static int nms_batched(const me_nms_desc* d, void* stream_, int prepped) {

@@ -218,6 +218,8 @@ class DetectorTrainer16:
     def forward(self, x):
         if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
             raise hip.MeError("Darknet training forward needs a 4-D CUDA float32 tensor; there is no CPU fallback")
+        if x.shape[2] != x.shape[3]:   # (rectangular frames are an inference feature of the engine: the YOLO loss kernels take one g)
+            raise hip.MeError(f"Darknet training forward needs square frames, got {x.shape[2]} x {x.shape[3]}")
         m, lib, half = self.m, hip.lib(), self.half
         eng = m.engine   # (the fp32 engine owns the packed master weights)
         x = x.contiguous()

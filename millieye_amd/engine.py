@@ -379,8 +379,22 @@ class DarknetEngine:
         allocate the arena, fill the launch descriptors, attach the scratch buffers and let the measured choices in."""
         defs, tap = self.model.module_defs, self.tap_module
         half = self.dtype in _TORCH_HALF  # any 16-bit storage mode
-        ops, tensors, out, yolo_rows = planner.lower(defs, int(self.model.hyperparams["channels"]), h, w, tap, half, keep_raw,
-                                                     decode_last=os.environ.get("MILLIEYE_DECODE_LAST", "1") != "0")
+        if h != w:
+            # rectangular frames (no reference counterpart - its YOLOLayer has one grid_size): Darknet's rule, every scale keeps
+            # one stride for both axes, so both sides are multiples of the largest one; inference only (the YOLO loss is square)
+            s = planner.max_stride(defs)
+            if h % s or w % s:
+                raise hip.MeError(f"Darknet input {h} x {w}: both sides of a rectangular input must be multiples of the cfg's "
+                                  f"largest stride ({s})")
+            if keep_raw:
+                raise hip.MeError(f"Darknet input {h} x {w}: the YOLO loss (targets) needs square inputs")
+        try:
+            ops, tensors, out, yolo_rows = planner.lower(defs, int(self.model.hyperparams["channels"]), h, w, tap, half, keep_raw,
+                                                         decode_last=os.environ.get("MILLIEYE_DECODE_LAST", "1") != "0", rect=True)
+        except ValueError as exc:
+            if h == w:
+                raise
+            raise hip.MeError(f"Darknet input {h} x {w}: {exc}") from exc
         tap_tensor = out[tap] if tap is not None and tap < len(defs) else None
         total = planner.place(ops, tensors, n, tap_tensor, keep_raw)
 
@@ -418,6 +432,9 @@ class DarknetEngine:
         plan.input_descs = []
         plan.yolo_raw = []  # raw detection maps [n,g,g,A*(5+C)] (arena views) for the YOLO loss
         plan.yolo_descs = []
+        # a rectangular grid: the _rect descriptors and entry points (``force_rect``: square plans through them as well - the
+        # cross-check of the two sets, tests/test_gpu_rect.py; clear ``_plans`` after changing it)
+        plan.yolo_rect = self.__dict__.get("force_rect", False) or any(op["kind"] == "yolo" and "g" not in op for op in ops)
         plan.conv_descs = []
         plan.conv_flops = 0
         plan.launches = launches = []
@@ -453,7 +470,7 @@ class DarknetEngine:
                 args = (*_view(plan, x), *_view(plan, y), n * x.h * x.w, x.c)
             elif kind == "yolo":
                 dsc = self._yolo_desc(plan, op)
-                fn = lib.me_yolo_decode_f32
+                fn = lib.me_yolo_decode_rect_f32 if plan.yolo_rect else lib.me_yolo_decode_f32
             launches.append((fn, args if dsc is None else (C.byref(dsc),), dsc, f"{kind}{op['module']}"))
         k = len(plan.yolo_descs)
         plan.yolo_tail = None  # the decodes are the last launches: Network.forward's candidate-list decode takes them in one launch
@@ -497,12 +514,18 @@ class DarknetEngine:
         na, nc = yl.num_anchors, yl.num_classes
         if x.c != na * (nc + 5):
             raise ValueError(f"yolo {i}: {x.c} channels != {na}*({nc}+5)")
-        dsc = hip.YoloDesc()
+        # square plans: the descriptor and the entry points they always had; a plan with a rectangular grid takes the _rect twins
+        # for all of its scales (one descriptor type per candidate-list launch)
+        dsc = hip.YoloRectDesc() if plan.yolo_rect else hip.YoloDesc()
         dsc.x, dsc.x_pitch = _view(plan, x)
         dsc.out = None
-        dsc.n, dsc.g, dsc.num_anchors, dsc.num_classes = plan.n, op["g"], na, nc
+        dsc.n, dsc.num_anchors, dsc.num_classes = plan.n, na, nc
+        if plan.yolo_rect:
+            dsc.gh, dsc.gw = op["gh"], op["gw"]
+        else:
+            dsc.g = op["g"]
         dsc.rows_total, dsc.row_offset = plan.rows, op["row_offset"]
-        stride = plan.h / op["g"]
+        stride = plan.h / op["gh"]   # == plan.w / op["gw"] (planner.lower refuses anything else)
         dsc.stride = stride
         for k, (aw, ah) in enumerate(yl.anchors):
             dsc.anchors[2 * k] = aw / stride
@@ -511,8 +534,8 @@ class DarknetEngine:
         plan.yolo_descs.append(dsc)
         plan.yolo_raw.append(_typed_view(plan, x, nchw=False))
         # side effects the reference's YOLOLayer.forward has (models.py:135-156)
-        yl.img_dim = plan.h
-        yl.grid_size = op["g"]
+        yl.img_dim = plan.h if plan.h == plan.w else (plan.h, plan.w)
+        yl.grid_size = op["g"] if "g" in op else (op["gh"], op["gw"])
         yl.stride = stride
         return dsc
 
@@ -612,13 +635,18 @@ class DarknetEngine:
             dsc.out = yp
         stream = hip.stream_ptr()
         first = 1
-        decode_cand = hip.lib().me_yolo_decode_cand_f32 if cand is not None else None
+        decode_cand = None
+        if cand is not None:
+            lib = hip.lib()
+            if plan.yolo_rect:
+                decode_cand, decode_multi = lib.me_yolo_decode_cand_rect_f32, lib.me_yolo_decode_cand_multi_rect_f32
+            else:
+                decode_cand, decode_multi = lib.me_yolo_decode_cand_f32, lib.me_yolo_decode_cand_multi_f32
         for fn, args, _keep, name in plan.launches:
             if decode_cand is not None and name.startswith("yolo"):
                 if plan.yolo_tail is not None:
                     if first:
-                        rc = hip.lib().me_yolo_decode_cand_multi_f32(plan.yolo_tail, len(plan.yolo_tail), cand[0], cand[1], 1,
-                                                                     stream)
+                        rc = decode_multi(plan.yolo_tail, len(plan.yolo_tail), cand[0], cand[1], 1, stream)
                     else:
                         continue
                 else:

@@ -81,6 +81,18 @@ class YoloDesc(C.Structure):
     ]
 
 
+class YoloRectDesc(C.Structure):
+    """``me_yolo_rect_desc``: :class:`YoloDesc` with ``gh, gw`` in the place of ``g`` (rectangular grids)."""
+    _fields_ = [
+        ("x", C.c_void_p), ("out", C.c_void_p),
+        ("x_pitch", C.c_int64),
+        ("n", C.c_int32), ("gh", C.c_int32), ("gw", C.c_int32), ("num_anchors", C.c_int32), ("num_classes", C.c_int32),
+        ("rows_total", C.c_int32), ("row_offset", C.c_int32),
+        ("stride", C.c_float),
+        ("anchors", C.c_float * 16),
+    ]
+
+
 class NmsDesc(C.Structure):
     _fields_ = [
         ("pred", C.c_void_p), ("det", C.c_void_p), ("count", C.c_void_p), ("workspace", C.c_void_p),
@@ -194,7 +206,7 @@ class AdamDesc(C.Structure):
 
 
 _STRUCTS = {0: ConvDesc, 1: PoolDesc, 2: YoloDesc, 3: NmsDesc, 4: HeadsDesc, 5: HeadsWeights, 6: Conv16Desc, 7: PackDesc,
-            8: Bneck16Desc, 9: AdamDesc, 10: RadarDesc, 11: NmsPythonDesc}
+            8: Bneck16Desc, 9: AdamDesc, 10: RadarDesc, 11: NmsPythonDesc, 12: YoloRectDesc}
 
 # name -> (restype, argtypes); every symbol include/millieye_hip.h declares
 SIGNATURES = {
@@ -249,6 +261,7 @@ SIGNATURES = {
     "me_nhwc_to_nchw_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_void_p]),
     "me_yolo_decode_f32": (C.c_int, [C.POINTER(YoloDesc), C.c_void_p]),
+    "me_yolo_decode_rect_f32": (C.c_int, [C.POINTER(YoloRectDesc), C.c_void_p]),
     "me_nms_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "me_nms_candidate_counts": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "me_nms_batched_f32": (C.c_int, [C.POINTER(NmsDesc), C.c_void_p]),
@@ -332,6 +345,8 @@ SIGNATURES = {
                                + [C.c_void_p, C.c_int64, C.c_void_p]),
     "me_yolo_decode_cand_f32": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),
     "me_yolo_decode_cand_multi_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),
+    "me_yolo_decode_cand_rect_f32": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),
+    "me_yolo_decode_cand_multi_rect_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),
     "me_nms_batched_prepped_f32": (C.c_int, [C.c_void_p, C.c_void_p]),
     "me_conv_wgrad_mfma_oihw_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int32] * 8
                                     + [C.c_void_p, C.c_int64, C.c_void_p]),
@@ -799,24 +814,42 @@ def nhwc_to_nchw(x_nhwc):
 
 
 def yolo_decode(x_nhwc, anchors, num_classes, img_dim, out=None, rows_total=None, row_offset=0):
-    """x_nhwc [N,G,G,A*(5+C)] -> rows of out [N,rows_total,5+C] (reference YOLOLayer decode)."""
+    """x_nhwc [N,G,G,A*(5+C)] -> rows of out [N,rows_total,5+C] (reference YOLOLayer decode).  ``img_dim``: the frame's side, or
+    ``(H, W)`` for a rectangular map [N,gh,gw,A*(5+C)] (``me_yolo_decode_rect_f32``: Darknet's rule, one stride = H / gh = W / gw,
+    row ``a * gh * gw + gy * gw + gx``; the reference's layer has no such case).  A non-square map needs ``(H, W)``."""
     _require_cuda_f32(x_nhwc, "x")
-    n, g, _, ch = x_nhwc.shape
+    n, gh, gw, ch = x_nhwc.shape
     na = len(anchors)
+    if isinstance(img_dim, (tuple, list)):
+        ih, iw = img_dim
+    else:
+        ih = iw = img_dim
+        if gh != gw:
+            raise MeError(f"yolo_decode: a {gh} x {gw} detection map needs img_dim=(H, W), got {img_dim!r}")
+    if ih * gw != iw * gh:
+        raise MeError(f"yolo_decode: a {gh} x {gw} detection map of a {ih} x {iw} frame has two strides ({ih / gh} and {iw / gw})")
     if rows_total is None:
-        rows_total = na * g * g
+        rows_total = na * gh * gw
     if out is None:
         out = torch.empty((n, rows_total, 5 + num_classes), device=x_nhwc.device, dtype=torch.float32)
-    d = YoloDesc()
+    rect = gh != gw
+    d = YoloRectDesc() if rect else YoloDesc()
     d.x, d.out, d.x_pitch = x_nhwc.data_ptr(), out.data_ptr(), ch
-    d.n, d.g, d.num_anchors, d.num_classes = n, g, na, num_classes
+    d.n, d.num_anchors, d.num_classes = n, na, num_classes
+    if rect:
+        d.gh, d.gw = gh, gw
+    else:
+        d.g = gh
     d.rows_total, d.row_offset = rows_total, row_offset
-    stride = img_dim / g
+    stride = ih / gh
     d.stride = stride
     for k, (aw, ah) in enumerate(anchors):
         d.anchors[2 * k] = aw / stride
         d.anchors[2 * k + 1] = ah / stride
-    check(lib().me_yolo_decode_f32(C.byref(d), stream_ptr()), "me_yolo_decode_f32")
+    if rect:
+        check(lib().me_yolo_decode_rect_f32(C.byref(d), stream_ptr()), "me_yolo_decode_rect_f32")
+    else:
+        check(lib().me_yolo_decode_f32(C.byref(d), stream_ptr()), "me_yolo_decode_f32")
     return out
 
 

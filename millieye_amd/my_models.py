@@ -544,7 +544,23 @@ class Network(nn.Module):
         each filtered to its frames: first the refined rows of the mode-0 frames by confidence, then the unrefined class-
         ``class_idx`` proposals of the mode-1 frames, image-major in NMS order.  ``radar_boxes_location[:, 1:]`` is ALWAYS
         scaled in place with ``frame_modes`` - also when every frame is camera only, where a scalar mode-1 call leaves it
-        alone.  ``model_mode`` must stay 0, ``targets`` None and the head BatchNorms in eval() mode (``hip.MeError``)."""
+        alone.  ``model_mode`` must stay 0, ``targets`` None and the head BatchNorms in eval() mode (``hip.MeError``).
+
+        Rectangular ``images`` [N,3,H,W] (H, W multiples of the detector's largest stride; no reference counterpart) work in
+        modes 0, 1 and 2: ``radar_boxes_location[:, 1:]`` is then scaled in place by ``(W, H, W, H)``, ``maps`` is [N,3,mh,mw];
+        ``targets``, train-mode heads and ``frame_modes`` need square frames (``hip.MeError``)."""
+        rect = images.dim() == 4 and images.shape[2] != images.shape[3]
+        if rect:
+            # rectangular frames [N,3,H,W] (no reference counterpart): inference in modes 0, 1 and 2; the detector's rows follow
+            # Darknet's rectangular rule (engine.py), the radar boxes are scaled per axis below, everything behind already takes
+            # the two map sizes separately
+            shape = f"{images.shape[2]} x {images.shape[3]}"
+            if frame_modes is not None:
+                raise hip.MeError(f"Network.forward: frame_modes needs square frames, got {shape}")
+            if targets is not None or isinstance(model_mode, torch.Tensor):
+                raise hip.MeError(f"Network.forward: targets (the training call) need square frames, got {shape}")
+            if model_mode != 1 and all(b.training for b in self._head_bns()):
+                raise hip.MeError(f"Network.forward: head BatchNorms in train() mode need square frames, got {shape}")
         if frame_modes is not None:
             if not images.is_cuda:
                 raise hip.MeError("Network.forward needs CUDA tensors (MI355X); there is no CPU fallback")
@@ -643,7 +659,11 @@ class Network(nn.Module):
 
         # ---- RoIs: image proposals then radar proposals (reference :490-492)
         if len(radar_boxes_location) > 0:
-            radar_boxes_location[:, 1:] *= images.shape[-1]  # in place on the caller's tensor, like the reference
+            if rect:   # x by W, y by H - in place on the caller's tensor as well
+                radar_boxes_location[:, 1:] *= radar_boxes_location.new_tensor(
+                    [images.shape[3], images.shape[2], images.shape[3], images.shape[2]])
+            else:
+                radar_boxes_location[:, 1:] *= images.shape[-1]  # in place on the caller's tensor, like the reference
         n_radar = int(radar_boxes_location.shape[0])
         rb = radar_boxes_location.to(**f32).contiguous() if n_radar else None
         cap = cap_img + n_radar

@@ -94,14 +94,34 @@ def _sources(module_defs):
     return srcs, readers
 
 
-def lower(module_defs, channels, h, w, tap, half, keep_raw, decode_last=True):
+def max_stride(module_defs):
+    """The largest downsampling factor a ``[yolo]`` block of the cfg sees (32 for every cfg in ``cfgs.py``): rectangular inputs
+    must be multiples of it in both axes, or the scales would not share one stride per axis."""
+    srcs, _readers = _sources(module_defs)
+    factor, best = [], 1
+    for i, d in enumerate(module_defs):
+        f = factor[srcs[i][0]] if srcs[i][0] >= 0 else 1
+        t = d["type"]
+        if t == "convolutional" or (t == "maxpool" and int(d["stride"]) > 1):
+            f = f * int(d["stride"])
+        elif t == "upsample":
+            f = f / int(d["stride"])
+        elif t == "yolo":
+            best = max(best, int(f))
+        factor.append(f)
+    return best
+
+
+def lower(module_defs, channels, h, w, tap, half, keep_raw, decode_last=True, rect=False):
     """cfg blocks -> ``(ops, tensors, out, yolo_rows)``: the op dicts in launch order, every ``_Tensor`` they touch (the network
     input first), ``out[i]`` = the tensor module ``i`` leaves behind (None: fused away / decoded rows) and the rows per [yolo].
 
     ``conv -> [shortcut]`` and ``conv -> [upsample x2]`` become one op when nobody else reads the intermediate (``tap`` counts as
     a reader); a multi-layer ``[route]`` makes its parts channel slices of one wider tensor (a ``copy`` op where a part already is
     a slice of another).  ``half`` (16-bit storage): activations take 2 bytes, channel counts are padded to multiples of 32 and the
-    maps that feed only ``[yolo]`` stay fp32.  ``decode_last``: the [yolo] ops go behind the last convolution."""
+    maps that feed only ``[yolo]`` stay fp32.  ``decode_last``: the [yolo] ops go behind the last convolution.  ``rect``: accept
+    ``h != w`` (a yolo op then carries ``gh, gw``, and ``g`` only when the two are equal; every scale must keep one stride,
+    ``h / gh == w / gw``); without it a non-square input is refused, as the reference's ``grid_size`` would."""
     defs, L = module_defs, len(module_defs)
     srcs, readers = _sources(defs)
     if half and keep_raw:
@@ -164,12 +184,18 @@ def lower(module_defs, channels, h, w, tap, half, keep_raw, decode_last=True):
             out[i] = _lower_route(i, [out[s] for s in srcs[i]], ops, new_tensor)
         elif t == "yolo":
             x = out[i - 1]
-            if x.h != x.w or h != w:
+            if not rect and (x.h != x.w or h != w):
                 raise ValueError("YOLO decode needs square inputs (the reference uses one grid_size)")
+            if h * x.w != w * x.h:  # one stride for both axes: H / gh == W / gw (Darknet's rectangular rule)
+                raise ValueError(f"yolo {i}: a {x.h} x {x.w} detection map of a {h} x {w} input has two strides "
+                                 f"({h / x.h} and {w / x.w})")
             if x.esize != 4:
                 raise RuntimeError(f"yolo {i}: the detection map is shared with another reader (bf16 mode)")
-            ops.append(dict(kind="yolo", module=i, x=x, g=x.h, row_offset=sum(yolo_rows)))
-            yolo_rows.append(len(d["mask"].split(",")) * x.h * x.h)
+            op = dict(kind="yolo", module=i, x=x, gh=x.h, gw=x.w, row_offset=sum(yolo_rows))
+            if x.h == x.w:
+                op["g"] = x.h
+            ops.append(op)
+            yolo_rows.append(len(d["mask"].split(",")) * x.h * x.w)
             out[i] = None  # decoded rows are never routed
         i += 1
 

@@ -74,11 +74,23 @@ class YOLOLayer(nn.Module):
 
     def forward(self, x, targets=None, img_dim=None):
         """Stand-alone use on one raw detection map ``x`` [N, A*(5+C), G, G] (NCHW, as the reference
-        passes it): returns ``(output [N, A*G*G, 5+C], 0)`` or, with ``targets``, ``(output, loss)``."""
+        passes it): returns ``(output [N, A*G*G, 5+C], 0)`` or, with ``targets``, ``(output, loss)``.
+        ``img_dim=(H, W)`` decodes a rectangular map [N, A*(5+C), gh, gw] (no reference counterpart; ``hip.yolo_decode``):
+        ``grid_size`` is then ``(gh, gw)``; a non-square map with an int ``img_dim``, or with ``targets``, is a ``hip.MeError``."""
         from .. import hip
         self.img_dim = img_dim if img_dim is not None else self.img_dim
-        self.grid_size = x.size(2)
-        self.stride = self.img_dim / self.grid_size
+        if isinstance(self.img_dim, (tuple, list)) and self.img_dim[0] == self.img_dim[1] and x.size(2) == x.size(3):
+            self.img_dim = self.img_dim[0]
+        if x.size(2) != x.size(3):
+            if not isinstance(self.img_dim, (tuple, list)):
+                raise hip.MeError(f"YOLOLayer: a {x.size(2)} x {x.size(3)} detection map needs img_dim=(H, W), got {self.img_dim!r}")
+            if targets is not None:
+                raise hip.MeError(f"YOLOLayer: the YOLO loss needs a square detection map, got {x.size(2)} x {x.size(3)}")
+            self.grid_size = (x.size(2), x.size(3))
+            self.stride = self.img_dim[0] / x.size(2)
+        else:
+            self.grid_size = x.size(2)
+            self.stride = (self.img_dim[0] if isinstance(self.img_dim, (tuple, list)) else self.img_dim) / self.grid_size
         nhwc = x.permute(0, 2, 3, 1).contiguous()
         output = hip.yolo_decode(nhwc, self.anchors, self.num_classes, self.img_dim)
         if targets is None:
@@ -96,6 +108,9 @@ class YOLOLayer(nn.Module):
             raise hip.MeError("YOLOLayer.loss_from_raw needs CUDA tensors (MI355X); there is no CPU fallback")
         import ctypes as C
         n, g = raw_nhwc.shape[0], raw_nhwc.shape[1]
+        if raw_nhwc.shape[2] != g or isinstance(self.img_dim, (tuple, list)):
+            raise hip.MeError(f"YOLOLayer.loss_from_raw needs a square detection map of a square frame, got a "
+                              f"{g} x {raw_nhwc.shape[2]} map with img_dim {self.img_dim!r}")
         dev, na, nc = raw_nhwc.device, self.num_anchors, self.num_classes
         raw = raw_nhwc
         if raw.dtype != torch.float32 or raw.stride(3) != 1 or raw.stride(1) != g * raw.stride(2) or \
@@ -268,6 +283,13 @@ class Darknet(nn.Module):
         ``loss`` is the summed YOLO loss of every scale (reference :261-267).  Under autograd with parameters that require
         gradients the loss is differentiable (``_forward_train``: millieye_amd/detector_train.py, or - ``compute_dtype`` "bf16" /
         "f16" - the mixed-precision step of millieye_amd/detector_train16.py); otherwise it is a value."""
+        if x.dim() == 4 and x.shape[2] != x.shape[3]:
+            # rectangular frames [N,3,H,W] (no reference counterpart - its YOLOLayer has one grid_size): inference on the engine
+            if targets is not None:
+                raise hip.MeError(f"Darknet.forward: targets (the YOLO loss) need square frames, got {x.shape[2]} x {x.shape[3]}")
+            if self._any_bn_training():
+                raise hip.MeError(f"Darknet.forward: BatchNorm in train() mode needs square frames, got {x.shape[2]} x "
+                                  f"{x.shape[3]} (rectangular frames run on the inference engine only)")
         if targets is not None and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             return self._forward_train(x, targets)
         if self._any_bn_training():
