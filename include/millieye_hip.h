@@ -767,6 +767,42 @@ int me_image_batch_area_u8_f32(const uint8_t* src, int64_t src_bytes, const int6
                                int32_t size, void* stream);
 int me_radar_heatmap_f32(const double* points, const int32_t* offsets, const int32_t* sizes, int32_t n,
                          int32_t radar_maps_size, float* out, int32_t map_size, void* stream);
+/* ---- letterbox to a rectangular canvas (the input side of the rectangular network; the reference's YOLOLayer has one
+ * grid_size, so its scripts have no counterpart: the pins are stock torch CPU ops) -------------------------------------------
+ * Geometry, one rule for frames, heat maps, radar boxes and the box rescale (utils.utils.letterbox_geometry on the host): for a
+ * picture h x w and a canvas H x W let g = gcd(H, W), a = H / g, b = W / g, k = max(ceil(h / a), ceil(w / b)) (64 bits).  The
+ * padded rectangle Ph = a k, Pw = b k is the smallest one of the canvas's aspect ratio that holds the picture, Ph / H == Pw / W
+ * exactly.  top = (Ph - h) / 2, left = (Pw - w) / 2 rounded down; the remainder goes behind; both axes may be padded; the pad
+ * value is 0.  The resize is then ONE F.interpolate(padded, size=(H, W)).  H == W: pad_to_square (a = b = 1, k = max(h, w)).
+ *
+ * me_image_batch_letterbox_u8_f32: me_image_batch_formats_u8_f32 - the same src, desc [n,5], formats, integer YUV conversion,
+ *   validity rules (an invalid frame comes out all zero and is never read), one launch with blockIdx.y = frame - writing
+ *   dst [n,3,height,width] float32 = F.interpolate(F.pad(u8 / 255), size=(height, width), mode="nearest"), bit for bit:
+ *     py = (Ph == height) ? y : min((int)floorf((float)y * ((float)Ph / (float)height)), Ph - 1), px likewise with Pw, width;
+ *     flip mirrors the padded rectangle: px = Pw - 1 - px;  sy = py - top, sx = px - left;  value = (float)c / 255.f.
+ *   A frame with Ph or Pw above 2^30 is invalid as well.  float4 stores per channel when width % 4 == 0 (dst 16-byte aligned,
+ *   ME_E_ALIGN otherwise), one pixel per thread otherwise; height * width < 2^30, n <= 65535.  For height == width the output
+ *   is bit-identical to me_image_batch_formats_u8_f32's.
+ * me_radar_heatmap_rect_f32: me_radar_heatmap_f32 with out [n,3,map_h,map_w].  The histogram half is unchanged (the bins
+ *   bh x bw of the original image); the bin map is padded by the rule above with (a, b) from gcd(map_h, map_w) and resized with
+ *   bilinear align_corners=True, rs_y = (Ph - 1) / (map_h - 1), rs_x = (Pw - 1) / (map_w - 1) (0 when that side is 1); the
+ *   identity shortcut applies only when Ph == map_h and Pw == map_w.  map_h == map_w gives the bits of me_radar_heatmap_f32.
+ *   map_h * map_w < 2^28, and a map whose reduced sides a, b would pad the bins beyond 2^30 (64 a or 64 b above 2^30, e.g.
+ *   1 x 2^27) is refused with ME_E_TOOBIG.
+ * me_radar_boxes_letterbox_f32 (csrc/radar.hip): the radar_boxes_location rows of Network.forward for a height x width canvas
+ *   from what me_radar_proposals_f64 left on the device: proposals [streams, MAX_TRACKS, 4] float64 pixel boxes, counts
+ *   [streams, 8] (column 7 = pixel proposals), frame_size [streams, 2] = (w, h).  The chain's last step per axis, in its float32
+ *   operations: (float)p + left | top | right | bottom, / (float)Pw for x and / (float)Ph for y, clamp to [0, 1] keeping NaN,
+ *   boxes with x1 >= x2 or y1 >= y2 dropped.  boxes [2 * streams * MAX_TRACKS, 5] float32: the first box_counts[streams] rows
+ *   are (stream, x1, y1, x2, y2) stream-major, the second half is scratch; box_counts [streams + 1] int32 = the kept boxes per
+ *   stream, then their total (the kept set can differ from the square chain's counts column 4).  Two launches, no host
+ *   read-back; the tracker state and me_radar_desc are not touched.  height == width: the chain's own rows and counts. */
+int me_image_batch_letterbox_u8_f32(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int32_t n, float* dst,
+                                    int32_t height, int32_t width, void* stream);
+int me_radar_heatmap_rect_f32(const double* points, const int32_t* offsets, const int32_t* sizes, int32_t n,
+                              int32_t radar_maps_size, float* out, int32_t map_h, int32_t map_w, void* stream);
+int me_radar_boxes_letterbox_f32(const double* proposals, const int32_t* counts, const int32_t* frame_size, int32_t streams,
+                                 int32_t height, int32_t width, float* boxes, int32_t* box_counts, void* stream);
 
 /* ---- multi-stream front of the live demos (csrc/radar.hip) ----------------------------------
  * me_radar_proposals_f64: the per-frame radar proposal chain of module3_our_dataset/run_mp.py:65-135 (= run_sp.py:117-175)

@@ -10,6 +10,10 @@
 //                               or a decoder hands over, without the host's conversion to RGB (run_mp.py:50,114).
 //   me_image_batch_area_u8_f32  the same ragged batch with F.interpolate(mode="area") for the resize: an option the reference's
 //                               scripts do not have, pinned to torch's float64 area interpolation (exact integer sums).
+//   me_image_batch_letterbox_u8_f32
+//                               the same ragged batch letterboxed to a rectangular H x W canvas (letterbox.h), for the
+//                               rectangular network input; torch's F.pad + F.interpolate(nearest) bit for bit.
+//   me_radar_heatmap_rect_f32   me_radar_heatmap_f32 with a rectangular mh x mw output (the bins letterboxed the same way).
 //   me_radar_heatmap_f32        plot_radar_heatmap (:59-106: three np.histogram2d in float64, per-bin means, range
 //                               normalisation) + ToTensor().float() (:267) + pad_to_square (:270) +
 //                               F.interpolate(bilinear, align_corners=True) to the map size (:318-321).
@@ -18,6 +22,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "letterbox.h"
 
 // every product / sum below is a separately rounded IEEE operation in the reference (numpy float64, aten float32
 // scalar kernels): no fused multiply-add contraction
@@ -137,15 +142,9 @@ __device__ inline void yuv_to_rgb(int Y, int U, int V, int& r, int& g, int& b) {
   b = clamp_u8((y + (1 << 19) + 2116026 * u) >> 20);
 }
 
-__global__ __launch_bounds__(256) void image_batch_formats_kernel(const unsigned char* __restrict__ src,
-                                                                  long long src_bytes,
-                                                                  const long long* __restrict__ desc,
-                                                                  float* __restrict__ dst, int S) {
-  const int f = blockIdx.y;
-  const long long off = desc[5 * f], h64 = desc[5 * f + 1], w64 = desc[5 * f + 2], fmt64 = desc[5 * f + 4];
-  const int flip = desc[5 * f + 3] != 0;
-  // a descriptor that does not lie inside the packed buffer, names no format or breaks its format's parity rule reads
-  // nothing: the frame comes out as padding.  The size test divides, so that no product of descriptor values can overflow.
+// The validity rule of a [n,5] descriptor row: a frame that does not lie inside the packed buffer, names no format or breaks
+// its format's parity rule.  The size test divides, so that no product of descriptor values can overflow.
+__device__ inline bool format_frame_valid(long long off, long long h64, long long w64, long long fmt64, long long src_bytes) {
   bool valid = h64 > 0 && w64 > 0 && h64 <= (1ll << 30) && w64 <= (1ll << 30) && off >= 0 && off <= src_bytes;
   const long long avail = src_bytes - off;
   if (fmt64 == ME_PIXFMT_RGB || fmt64 == ME_PIXFMT_BGR)
@@ -156,6 +155,36 @@ __global__ __launch_bounds__(256) void image_batch_formats_kernel(const unsigned
     valid = valid && (w64 & 1) == 0 && h64 <= avail / (2 * w64);
   else
     valid = false;
+  return valid;
+}
+
+// 8-bit R, G, B of picture pixel (sy, sx) of a valid frame in format fmt
+__device__ inline void fetch_rgb_u8(const unsigned char* __restrict__ frame, int h, int w, int fmt, int sy, int sx, int& ri,
+                                    int& gi, int& bi) {
+  if (fmt == ME_PIXFMT_RGB || fmt == ME_PIXFMT_BGR) {
+    const unsigned char* p = frame + ((size_t)sy * w + sx) * 3;
+    ri = fmt == ME_PIXFMT_RGB ? p[0] : p[2];
+    gi = p[1];
+    bi = fmt == ME_PIXFMT_RGB ? p[2] : p[0];
+  } else if (fmt == ME_PIXFMT_NV12) {   // Y plane [h,w], then the interleaved UV plane [h/2,w]
+    const unsigned char* uv = frame + (size_t)h * w + (size_t)(sy >> 1) * w + (sx & ~1);
+    yuv_to_rgb(frame[(size_t)sy * w + sx], uv[0], uv[1], ri, gi, bi);
+  } else {                              // YUYV: rows of Y0 U Y1 V
+    const unsigned char* row = frame + (size_t)sy * w * 2;
+    const int c = 4 * (sx >> 1);
+    yuv_to_rgb(row[2 * sx], row[c + 1], row[c + 3], ri, gi, bi);
+  }
+}
+
+__global__ __launch_bounds__(256) void image_batch_formats_kernel(const unsigned char* __restrict__ src,
+                                                                  long long src_bytes,
+                                                                  const long long* __restrict__ desc,
+                                                                  float* __restrict__ dst, int S) {
+  const int f = blockIdx.y;
+  const long long off = desc[5 * f], h64 = desc[5 * f + 1], w64 = desc[5 * f + 2], fmt64 = desc[5 * f + 4];
+  const int flip = desc[5 * f + 3] != 0;
+  // an invalid descriptor reads nothing: the frame comes out as padding
+  const bool valid = format_frame_valid(off, h64, w64, fmt64, src_bytes);
   const int h = valid ? (int)h64 : 1, w = valid ? (int)w64 : 1, fmt = (int)fmt64;
   const int P = h > w ? h : w;
   const int diff = h > w ? h - w : w - h;
@@ -175,19 +204,7 @@ __global__ __launch_bounds__(256) void image_batch_formats_kernel(const unsigned
     r = 0.f, g = 0.f, b = 0.f;
     if (valid && (unsigned)sy < (unsigned)h && (unsigned)sx < (unsigned)w) {
       int ri, gi, bi;
-      if (fmt == ME_PIXFMT_RGB || fmt == ME_PIXFMT_BGR) {
-        const unsigned char* p = frame + ((size_t)sy * w + sx) * 3;
-        ri = fmt == ME_PIXFMT_RGB ? p[0] : p[2];
-        gi = p[1];
-        bi = fmt == ME_PIXFMT_RGB ? p[2] : p[0];
-      } else if (fmt == ME_PIXFMT_NV12) {   // Y plane [h,w], then the interleaved UV plane [h/2,w]
-        const unsigned char* uv = frame + (size_t)h * w + (size_t)(sy >> 1) * w + (sx & ~1);
-        yuv_to_rgb(frame[(size_t)sy * w + sx], uv[0], uv[1], ri, gi, bi);
-      } else {                              // YUYV: rows of Y0 U Y1 V
-        const unsigned char* row = frame + (size_t)sy * w * 2;
-        const int c = 4 * (sx >> 1);
-        yuv_to_rgb(row[2 * sx], row[c + 1], row[c + 3], ri, gi, bi);
-      }
+      fetch_rgb_u8(frame, h, w, fmt, sy, sx, ri, gi, bi);
       r = (float)ri / 255.f;
       g = (float)gi / 255.f;
       b = (float)bi / 255.f;
@@ -208,6 +225,67 @@ __global__ __launch_bounds__(256) void image_batch_formats_kernel(const unsigned
   } else {
     for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
       const int y = idx / S, x = idx - y * S;
+      float r, g, b;
+      pixel(y, x, r, g, b);
+      out[idx] = r;
+      out[total + idx] = g;
+      out[2 * total + idx] = b;
+    }
+  }
+}
+
+// ---- ragged batch, letterbox to a rectangular canvas ---------------------------------------------------------------
+// image_batch_formats_kernel for an output of H x W.  With a = H / gcd(H, W), b = W / gcd(H, W) the padded rectangle is the
+// smallest (a k) x (b k) that holds the picture: k = max(ceil(h / a), ceil(w / b)) in 64 bits, Ph = a k, Pw = b k, so that
+// Ph / H == Pw / W exactly; floor(diff / 2) of the padding goes in front on each axis, the rest behind (letterbox.h).  Then
+// the nearest rule per axis.  H == W gives a = b = 1, Ph = Pw = max(h, w): the operations, and the bits, of image_batch_formats_kernel.
+__global__ __launch_bounds__(256) void image_batch_letterbox_kernel(const unsigned char* __restrict__ src,
+                                                                    long long src_bytes,
+                                                                    const long long* __restrict__ desc,
+                                                                    float* __restrict__ dst, int H, int W, int a, int b) {
+  const int f = blockIdx.y;
+  const long long off = desc[5 * f], h64 = desc[5 * f + 1], w64 = desc[5 * f + 2], fmt64 = desc[5 * f + 4];
+  const int flip = desc[5 * f + 3] != 0;
+  bool valid = format_frame_valid(off, h64, w64, fmt64, src_bytes);
+  const LetterboxGeom geo = letterbox_geom(valid ? (int)h64 : 1, valid ? (int)w64 : 1, a, b);
+  valid = valid && geo.ok;
+  const int h = valid ? (int)h64 : 1, w = valid ? (int)w64 : 1, fmt = (int)fmt64;
+  const int Ph = geo.Ph, Pw = geo.Pw, pad_top = geo.top, pad_left = geo.left;
+  const float scale_y = (float)Ph / (float)H, scale_x = (float)Pw / (float)W;
+  const int total = H * W;
+  const unsigned char* frame = src + (valid ? off : 0);
+  float* out = dst + (size_t)f * 3 * total;
+  auto pixel = [&](int y, int x, float& r, float& g, float& b) {
+    int py = Ph == H ? y : (int)floorf((float)y * scale_y);
+    int px = Pw == W ? x : (int)floorf((float)x * scale_x);
+    py = py < Ph - 1 ? py : Ph - 1;
+    px = px < Pw - 1 ? px : Pw - 1;
+    if (flip) px = Pw - 1 - px;
+    const int sy = py - pad_top, sx = px - pad_left;
+    r = 0.f, g = 0.f, b = 0.f;
+    if (valid && (unsigned)sy < (unsigned)h && (unsigned)sx < (unsigned)w) {
+      int ri, gi, bi;
+      fetch_rgb_u8(frame, h, w, fmt, sy, sx, ri, gi, bi);
+      r = (float)ri / 255.f;
+      g = (float)gi / 255.f;
+      b = (float)bi / 255.f;
+    }
+  };
+  if ((W & 3) == 0) {
+    for (int base = blockIdx.x * kBatchPix + threadIdx.x * 4; base < total; base += gridDim.x * kBatchPix) {
+      const int y = base / W, x0 = base - y * W;  // the 4 pixels share row y (W % 4 == 0, base % 4 == 0)
+      float4 r4, g4, b4;
+      pixel(y, x0, r4.x, g4.x, b4.x);
+      pixel(y, x0 + 1, r4.y, g4.y, b4.y);
+      pixel(y, x0 + 2, r4.z, g4.z, b4.z);
+      pixel(y, x0 + 3, r4.w, g4.w, b4.w);
+      *reinterpret_cast<float4*>(out + base) = r4;
+      *reinterpret_cast<float4*>(out + total + base) = g4;
+      *reinterpret_cast<float4*>(out + 2 * total + base) = b4;
+    }
+  } else {
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+      const int y = idx / W, x = idx - y * W;
       float r, g, b;
       pixel(y, x, r, g, b);
       out[idx] = r;
@@ -495,9 +573,13 @@ struct HeatP {
   const int* sizes;       // [n, 2] = (w, h) of the original image
   float* out;             // [n, 3, ms, ms]
   int maps_size;          // radar_maps_size (32)
-  int ms;                 // output side (img_size / 16)
+  int ms;                 // output side (img_size / 16); kRect: the output height mh
+  int mw, a, b;           // kRect only: the output width, a = mh / gcd(mh, mw), b = mw / gcd(mh, mw)
 };
 
+// kRect = false: me_radar_heatmap_f32.  kRect = true: me_radar_heatmap_rect_f32 - the same bins, padded to the smallest
+// (a k) x (b k) that holds them (letterbox_geom) and resized to mh x mw with one factor per axis.
+template <bool kRect>
 __global__ __launch_bounds__(256) void radar_heatmap_kernel(HeatP p) {
   __shared__ float maps[3][HM_MAX * HM_MAX];  // [c][y * bw + x], already float32 (ToTensor().float())
   const int f = blockIdx.x;
@@ -535,6 +617,36 @@ __global__ __launch_bounds__(256) void radar_heatmap_kernel(HeatP p) {
     maps[2][b] = (float)c2;
   }
   __syncthreads();
+  if constexpr (kRect) {
+    // bh, bw <= HM_MAX and the entry point refuses a * HM_MAX or b * HM_MAX above 2^30: Ph, Pw <= 2^30, geo.ok holds
+    const LetterboxGeom geo = letterbox_geom(bh, bw, p.a, p.b);
+    const int Ph = geo.Ph, Pw = geo.Pw, pad_top = geo.top, pad_left = geo.left, mh = p.ms, mw = p.mw;
+    const float rs_y = mh > 1 ? (float)(Ph - 1) / (float)(mh - 1) : 0.f;
+    const float rs_x = mw > 1 ? (float)(Pw - 1) / (float)(mw - 1) : 0.f;
+    auto at = [&](int c, int y, int x) -> float {
+      const int sy = y - pad_top, sx = x - pad_left;
+      return ((unsigned)sy < (unsigned)bh && (unsigned)sx < (unsigned)bw) ? maps[c][sy * bw + sx] : 0.f;
+    };
+    float* out = p.out + (size_t)f * 3 * mh * mw;
+    for (int idx = threadIdx.x; idx < 3 * mh * mw; idx += 256) {
+      const int c = idx / (mh * mw), rem = idx - c * mh * mw;
+      const int oy = rem / mw, ox = rem - oy * mw;
+      float v;
+      if (Ph == mh && Pw == mw) {
+        v = at(c, oy, ox);
+      } else {
+        const float h1r = rs_y * (float)oy, w1r = rs_x * (float)ox;
+        const int h1 = (int)h1r, w1 = (int)w1r;
+        const int h1p = h1 < Ph - 1 ? 1 : 0, w1p = w1 < Pw - 1 ? 1 : 0;
+        const float h1l = h1r - (float)h1, w1l = w1r - (float)w1;
+        const float h0l = 1.f - h1l, w0l = 1.f - w1l;
+        v = h0l * (w0l * at(c, h1, w1) + w1l * at(c, h1, w1 + w1p)) +
+            h1l * (w0l * at(c, h1 + h1p, w1) + w1l * at(c, h1 + h1p, w1 + w1p));
+      }
+      out[idx] = v;
+    }
+    return;
+  }
   // pad_to_square (zeros) + bilinear, align_corners=True (aten upsample_bilinear2d, float32 arithmetic)
   const int P = bh > bw ? bh : bw;
   const int diff = bh > bw ? bh - bw : bw - bh;
@@ -624,6 +736,23 @@ int me_image_batch_formats_u8_f32(const uint8_t* src, int64_t src_bytes, const i
   return me::check_launch("image_batch_formats_kernel");
 }
 
+int me_image_batch_letterbox_u8_f32(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int32_t n, float* dst,
+                                    int32_t height, int32_t width, void* stream) {
+  if (n == 0) return 0;
+  ME_REQUIRE(src && desc && dst, ME_E_NULLPTR, "me_image_batch_letterbox_u8_f32: null pointer");
+  ME_REQUIRE(n > 0 && n <= 65535 && height > 0 && width > 0 && src_bytes > 0, ME_E_BADARG,
+             "me_image_batch_letterbox_u8_f32: bad n / height / width / src_bytes");
+  ME_REQUIRE((long long)height * width < (1ll << 30), ME_E_TOOBIG, "me_image_batch_letterbox_u8_f32: output too large");
+  ME_REQUIRE((width & 3) != 0 || me::aligned16(dst), ME_E_ALIGN, "me_image_batch_letterbox_u8_f32: dst not 16-byte aligned");
+  const int per_block = (width & 3) == 0 ? kBatchPix : 256;
+  int tiles = (int)me::ceil_div((int64_t)height * width, per_block);
+  if (tiles > 1024) tiles = 1024;
+  const int g = me::gcd_i32(height, width);
+  hipLaunchKernelGGL(image_batch_letterbox_kernel, dim3(tiles, n), dim3(256), 0, (hipStream_t)stream, src,
+                     (long long)src_bytes, reinterpret_cast<const long long*>(desc), dst, height, width, height / g, width / g);
+  return me::check_launch("image_batch_letterbox_kernel");
+}
+
 int me_image_batch_area_u8_f32(const uint8_t* src, int64_t src_bytes, const int64_t* desc, int32_t n, float* dst,
                                int32_t size, void* stream) {
   if (n == 0) return 0;
@@ -644,8 +773,25 @@ int me_radar_heatmap_f32(const double* points, const int32_t* offsets, const int
   ME_REQUIRE(n > 0 && map_size > 0, ME_E_BADARG, "me_radar_heatmap_f32: bad n / map_size");
   ME_REQUIRE(radar_maps_size >= 1 && radar_maps_size <= HM_MAX, ME_E_BADARG,
              "me_radar_heatmap_f32: radar_maps_size %d outside [1, %d]", radar_maps_size, HM_MAX);
-  HeatP p{points, offsets, sizes, out, radar_maps_size, map_size};
-  hipLaunchKernelGGL(radar_heatmap_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, p);
+  HeatP p{points, offsets, sizes, out, radar_maps_size, map_size, 0, 0, 0};
+  hipLaunchKernelGGL(radar_heatmap_kernel<false>, dim3(n), dim3(256), 0, (hipStream_t)stream, p);
+  return me::check_launch("radar_heatmap_kernel");
+}
+
+int me_radar_heatmap_rect_f32(const double* points, const int32_t* offsets, const int32_t* sizes, int32_t n,
+                              int32_t radar_maps_size, float* out, int32_t map_h, int32_t map_w, void* stream) {
+  if (n == 0) return 0;
+  ME_REQUIRE(points && offsets && sizes && out, ME_E_NULLPTR, "me_radar_heatmap_rect_f32: null pointer");
+  ME_REQUIRE(n > 0 && map_h > 0 && map_w > 0, ME_E_BADARG, "me_radar_heatmap_rect_f32: bad n / map size %d x %d", map_h, map_w);
+  ME_REQUIRE((long long)map_h * map_w < (1ll << 28), ME_E_TOOBIG, "me_radar_heatmap_rect_f32: map %d x %d too large", map_h, map_w);
+  ME_REQUIRE(radar_maps_size >= 1 && radar_maps_size <= HM_MAX, ME_E_BADARG,
+             "me_radar_heatmap_rect_f32: radar_maps_size %d outside [1, %d]", radar_maps_size, HM_MAX);
+  const int g = me::gcd_i32(map_h, map_w);
+  // the padded bin map is at most (a HM_MAX) x (b HM_MAX): keep it within the geometry's 2^30 (1 x 2^27 would not be)
+  ME_REQUIRE((long long)(map_h / g) * HM_MAX <= (1ll << 30) && (long long)(map_w / g) * HM_MAX <= (1ll << 30), ME_E_TOOBIG,
+             "me_radar_heatmap_rect_f32: the aspect ratio of %d x %d pads the bins beyond 2^30", map_h, map_w);
+  HeatP p{points, offsets, sizes, out, radar_maps_size, map_h, map_w, map_h / g, map_w / g};
+  hipLaunchKernelGGL(radar_heatmap_kernel<true>, dim3(n), dim3(256), 0, (hipStream_t)stream, p);
   return me::check_launch("radar_heatmap_kernel");
 }
 

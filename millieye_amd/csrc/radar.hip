@@ -7,12 +7,16 @@
 //                        that stream's slots; a stream over a capacity sets its status and touches no state.
 //   radar_pack_kernel    slots -> the packed [total,5] boxes of Network.forward and the packed (points, offsets) of
 //                        me_radar_heatmap_f32.
+//   radar_boxes_letterbox_kernel / radar_boxes_pack_kernel
+//                        me_radar_boxes_letterbox_f32: the network boxes again, from the pixel proposals on the device, for a
+//                        rectangular canvas (letterbox.h: the padding and the divisor per axis).
 //   frame_means_kernel   one mean per frame (the auto mode's img.mean()).
 // Nothing here is throughput-bound (the demos have about 25 points, 3 clusters, 4 tracks per stream; tests/test_gpu_radar_chain.py
 // runs it at the capacities, 256 / 32 / 32); the point is that S streams cost two launches and no host loop.
 #include <stddef.h>
 
 #include "common.h"
+#include "letterbox.h"
 
 // the host code's float64 / float32 operations are rounded one by one: no fused multiply-add contraction
 #pragma clang fp contract(off)
@@ -665,6 +669,74 @@ __global__ __launch_bounds__(THREADS) void radar_pack_kernel(const int* __restri
   }
 }
 
+// ---- the network's radar boxes for a rectangular canvas ------------------------------------------------------------------------
+// The chain kernel's last block per axis, from what the chain left on the device: pixel proposals [streams, MAXT, 4], their
+// number counts[:, 7], frame_size [streams, 2] = (w, h).  The frame is letterboxed into the canvas (letterbox.h: Ph x Pw, the
+// padding split per axis), so x takes + left | right and / Pw, y takes + top | bottom and / Ph - the chain's float32 operations
+// in the chain's order; a = b = 1 (square canvas) gives the chain's own rows and counts.  One wave per stream writes slot s of
+// `slots` and box_counts[s]; the pack kernel moves the slots stream-major to the front and writes the total.
+constexpr int BOX_THREADS = 64;
+
+__global__ __launch_bounds__(BOX_THREADS) void radar_boxes_letterbox_kernel(const double* __restrict__ proposals,
+                                                                            const int* __restrict__ counts,
+                                                                            const int* __restrict__ frame_size, int a, int b,
+                                                                            float* __restrict__ slots,
+                                                                            int* __restrict__ box_counts) {
+  __shared__ float s_box[MAXT][4];
+  __shared__ int s_ok[MAXT];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  int np = counts[NCNT * s + 7];
+  np = np < 0 ? 0 : (np > MAXT ? MAXT : np);
+  const int fw = frame_size[2 * s], fh = frame_size[2 * s + 1];
+  const bool frame_ok = fw > 0 && fh > 0 && fw <= (1 << 30) && fh <= (1 << 30);
+  const LetterboxGeom geo = letterbox_geom(frame_ok ? fh : 1, frame_ok ? fw : 1, a, b);
+  if (!frame_ok || !geo.ok) np = 0;   // no canvas to normalise for: no boxes
+  if (tid < np) {
+    const double* p = proposals + ((size_t)s * MAXT + tid) * 4;
+    const float left = (float)geo.left, right = (float)(geo.Pw - fw - geo.left);
+    const float top = (float)geo.top, bottom = (float)(geo.Ph - fh - geo.top);
+    const float side_x = (float)geo.Pw, side_y = (float)geo.Ph;
+    float v[4] = {(float)p[0] + left, (float)p[1] + top, (float)p[2] + right, (float)p[3] + bottom};
+    for (int q = 0; q < 4; ++q) {
+      float val = v[q] / ((q & 1) ? side_y : side_x);
+      val = val < 0.f ? 0.f : val;   // torch.clamp keeps NaN
+      val = val > 1.f ? 1.f : val;
+      s_box[tid][q] = val;
+      v[q] = val;
+    }
+    s_ok[tid] = v[0] < v[2] && v[1] < v[3];
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int nb = 0;
+    float* out = slots + (size_t)s * MAXT * 5;
+    for (int k = 0; k < np; ++k) {
+      if (!s_ok[k]) continue;
+      out[nb * 5] = (float)s;
+      for (int q = 0; q < 4; ++q) out[nb * 5 + 1 + q] = s_box[k][q];
+      ++nb;
+    }
+    box_counts[s] = nb;
+  }
+}
+
+__global__ __launch_bounds__(THREADS) void radar_boxes_pack_kernel(const float* __restrict__ slots, int streams,
+                                                                   float* __restrict__ boxes, int* __restrict__ box_counts) {
+  __shared__ int s_sum[THREADS];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  int pb = 0;
+  for (int i = tid; i < s; i += THREADS) pb += box_counts[i];
+  s_sum[tid] = pb;
+  __syncthreads();
+  for (int step = THREADS / 2; step > 0; step >>= 1) {
+    if (tid < step) s_sum[tid] += s_sum[tid + step];
+    __syncthreads();
+  }
+  const int box0 = s_sum[0], nb = box_counts[s];
+  for (int e = tid; e < nb * 5; e += THREADS) boxes[(size_t)box0 * 5 + e] = slots[(size_t)s * MAXT * 5 + e];
+  if (tid == 0 && s == streams - 1) box_counts[streams] = box0 + nb;
+}
+
 // ---- per-frame means ---------------------------------------------------------------------------------------------------------
 constexpr int MEAN_THREADS = 1024;
 // modes (me_frame_modes_f32; nullptr = means only): the auto mode's rule on the mean just stored, compared in double like the
@@ -747,6 +819,25 @@ int me_radar_proposals_f64(const me_radar_desc* d, void* stream) {
   hipLaunchKernelGGL(radar_pack_kernel, dim3(d->streams), dim3(THREADS), 0, (hipStream_t)stream, d->counts, box_slots,
                      d->cloud_slots, d->streams, d->boxes, d->cloud, d->cloud_offsets, d->totals);
   return me::check_launch("radar_pack_kernel");
+}
+
+int me_radar_boxes_letterbox_f32(const double* proposals, const int32_t* counts, const int32_t* frame_size, int32_t streams,
+                                 int32_t height, int32_t width, float* boxes, int32_t* box_counts, void* stream) {
+  if (streams == 0) return 0;
+  ME_REQUIRE(proposals && counts && frame_size && boxes && box_counts, ME_E_NULLPTR, "me_radar_boxes_letterbox_f32: null pointer");
+  ME_REQUIRE(streams > 0 && streams <= 65535, ME_E_BADARG, "me_radar_boxes_letterbox_f32: %d streams", streams);
+  ME_REQUIRE(height > 0 && width > 0 && (long long)height * width < (1ll << 30), ME_E_BADARG,
+             "me_radar_boxes_letterbox_f32: bad canvas %d x %d", height, width);
+  // like the chain: a stream's boxes go to slot s of the buffer's second half, the pack kernel moves them to the front
+  float* slots = boxes + (size_t)streams * MAXT * 5;
+  const int g = me::gcd_i32(height, width);
+  hipLaunchKernelGGL(radar_boxes_letterbox_kernel, dim3(streams), dim3(BOX_THREADS), 0, (hipStream_t)stream, proposals, counts,
+                     frame_size, height / g, width / g, slots, box_counts);
+  int rc = me::check_launch("radar_boxes_letterbox_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(radar_boxes_pack_kernel, dim3(streams), dim3(THREADS), 0, (hipStream_t)stream, slots, streams, boxes,
+                     box_counts);
+  return me::check_launch("radar_boxes_pack_kernel");
 }
 
 int me_frame_means_f32(const float* imgs, int32_t n, int64_t elems_per_frame, float* means, void* stream) {

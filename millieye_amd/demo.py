@@ -17,6 +17,10 @@ cloud, per-frame means for the mode rule, at most two ``Network.forward`` calls 
 one pass over the network's rows for the output tail (``me_stream_tail_f32``: the second NMS of every stream and the rescale to
 its frame, one copy back).  ``pipeline.FusionPipeline`` runs its host half (:func:`prepare_streams`) in the producer process.
 
+``img_size=(H, W)`` on either fuser (and :func:`prepare_streams`) feeds the rectangular network: every frame, radar map and radar
+box is letterboxed by ``utils.utils.letterbox_geometry`` and the rows come back through the per-axis ``rescale_boxes``.  The
+reference has no counterpart (its ``YOLOLayer`` has one ``grid_size``); tests/letterbox_refs.py restates the step with stock torch.
+
 Parity: every numeric stage is one of the pinned pieces (input kernels: tests/golden/dataset_small; Network.forward:
 network_*.npz; NMS: nms_synth; radar proposals: radar_proposals_synth + the unpinned Kalman part); the glue in this file
 restates run_mp's inline code and has no fixture of its own.
@@ -28,7 +32,7 @@ from . import hip
 from .radar_proposals import DeviceRadarProposals, RadarProposalGenerator
 from .utils.datasets import (StagedImages, StagedRadarMaps, StagedRaggedImages, _pad_amounts, picture_hw, pixel_format_names,
                              resize_mode)
-from .utils.utils import box_ops, rescale_boxes, rescale_scalars
+from .utils.utils import box_ops, canvas_size, letterbox_geometry, rescale_boxes, rescale_scalars
 
 __all__ = ["mode_selection", "radar_boxes_for_network", "prepare_streams", "FrameFuser", "MultiStreamFuser"]
 
@@ -43,17 +47,38 @@ def mode_selection(mode, img, dark_threshold=0.08):
     return None  # the reference falls off the end for other values
 
 
-def radar_boxes_for_network(xyxy_pixels, frame_hw):
+def _network_input_size(img_size, what):
+    """``img_size`` of a fuser: an ``int`` is taken as it is (the square path, unchanged); ``(H, W)`` must have sides that are
+    positive multiples of 32 (``Network.forward``'s rule) and ``(S, S)`` becomes ``S``."""
+    return canvas_size(img_size, f"{what}: img_size", multiple=32) if isinstance(img_size, (tuple, list)) else img_size
+
+
+def _rect_map_size(img_size):
+    """The radar map of a rectangular input ``(H, W)``: the dataset's ``map_size = img_size / 16`` per side.  (The demos' raw
+    32 x 32 map, quirk q15, which the square fusers feed, has no rectangular form.)"""
+    return (img_size[0] // 16, img_size[1] // 16)
+
+
+def radar_boxes_for_network(xyxy_pixels, frame_hw, canvas=None):
     """Pixel boxes of the un-padded frame -> ``[k,5]`` rows ``(0, x1, y1, x2, y2)`` in units of the padded square side,
-    clamped to [0,1], empty boxes dropped (run_mp.py:119-135)."""
+    clamped to [0,1], empty boxes dropped (run_mp.py:119-135).
+
+    ``canvas=(H, W)``: the frame is letterboxed into a rectangular network input (``utils.utils.letterbox_geometry``): the
+    padding is split per axis, x is in units of the padded width ``Pw`` and y of the padded height ``Ph``.  ``(S, S)`` gives
+    what ``None`` gives."""
     h, w = frame_hw
     boxes = torch.as_tensor(np.asarray(xyxy_pixels, dtype=np.float32).reshape(-1, 4))
     if len(boxes) == 0:
         return torch.zeros((0, 5))
-    left, right, top, bottom = _pad_amounts(h, w)
-    side = float(max(h, w))
-    boxes = boxes + torch.tensor([left, top, right, bottom], dtype=torch.float32)
-    boxes = torch.clamp(boxes / side, 0, 1)
+    if canvas is not None:
+        Ph, Pw, top, left = letterbox_geometry((h, w), canvas)
+        boxes = boxes + torch.tensor([left, top, Pw - w - left, Ph - h - top], dtype=torch.float32)
+        boxes = torch.clamp(boxes / torch.tensor([Pw, Ph, Pw, Ph], dtype=torch.float32), 0, 1)
+    else:
+        left, right, top, bottom = _pad_amounts(h, w)
+        side = float(max(h, w))
+        boxes = boxes + torch.tensor([left, top, right, bottom], dtype=torch.float32)
+        boxes = torch.clamp(boxes / side, 0, 1)
     boxes = boxes[(boxes[:, 0] < boxes[:, 2]) & (boxes[:, 1] < boxes[:, 3])]
     out = torch.zeros((len(boxes), 5))
     out[:, 1:] = boxes
@@ -66,16 +91,25 @@ class FrameFuser:
 
     ``pixel_format``: a name of ``utils.datasets.PIXEL_FORMATS`` - the camera's native frame.  ``resize``: ``None`` /
     ``"nearest"`` (the reference's resize) or ``"area"`` (``F.interpolate(mode="area")``, an option the reference does not have;
-    semantics and range: ``StagedRaggedImages``).  Either one stages the frame through the ragged-batch kernels."""
+    semantics and range: ``StagedRaggedImages``).  Either one stages the frame through the ragged-batch kernels.
+
+    ``img_size=(H, W)`` (sides multiples of 32): the frame is letterboxed to the rectangular network input
+    (``utils.utils.letterbox_geometry``, ``me_image_batch_letterbox_u8_f32``), the radar boxes are normalised per axis, the radar
+    map is the dataset's resized ``(H / 16, W / 16)`` map (the raw 32 x 32 map of the square path has no rectangular form) and
+    the rows come back through the per-axis ``rescale_boxes``.  ``(S, S)`` is ``S``; ``resize="area"`` is refused."""
 
     def __init__(self, model, calib_param, model_mode=3, img_size=416, nms_iou=0.3, dark_threshold=0.08, generator=None,
                  pixel_format=None, resize=None, **generator_kwargs):
-        self.model, self.model_mode, self.img_size = model, model_mode, img_size
+        self.model, self.model_mode, self.img_size = model, model_mode, _network_input_size(img_size, "FrameFuser")
+        self.rect = isinstance(self.img_size, tuple)
         self.nms_iou, self.dark_threshold = nms_iou, dark_threshold
         # None: uint8 [h,w,3] RGB through the per-frame kernel; a name of utils.datasets.PIXEL_FORMATS: the camera's native
         # frame, staged through the ragged-batch kernel (bit-identical to the per-frame one on the converted frame)
         self.pixel_format = None if pixel_format is None else pixel_format_names(pixel_format, 1)[0]
         self.resize = resize_mode(resize, "FrameFuser")
+        if self.rect and self.resize == "area":
+            raise hip.MeError(f"FrameFuser: resize='area' has no rectangular form (img_size {self.img_size[0]} x "
+                              f"{self.img_size[1]})")
         self.generator_is_default = generator is None   # pipeline.py: re-created in the producer vs sent by pickle
         self.generator = generator or RadarProposalGenerator(calib_param, **generator_kwargs)
 
@@ -88,7 +122,7 @@ class FrameFuser:
     def prepare(self, frame, radar_frames):
         """Host half (run_mp.py:65-152 ``pre_process``): a picklable payload for :meth:`infer`."""
         frame = torch.as_tensor(frame)
-        if self.pixel_format is not None or self.resize == "area":
+        if self.pixel_format is not None or self.resize == "area" or self.rect:
             h, w = picture_hw(frame, self.pixel_format or "rgb")
             img = StagedRaggedImages([frame], self.img_size, formats=self.pixel_format, resize=self.resize).pack()
         else:
@@ -98,8 +132,9 @@ class FrameFuser:
             img = StagedImages([frame], self.img_size)
         proposals, cloud = self.generator(radar_frames)
         return dict(hw=(h, w), proposals=proposals, points=int(len(cloud)),
-                    radar_box=radar_boxes_for_network(proposals, (h, w)),
-                    img=img, radar_map=StagedRadarMaps([cloud], [(w, h)], map_size=32))
+                    radar_box=radar_boxes_for_network(proposals, (h, w), self.img_size if self.rect else None),
+                    img=img, radar_map=StagedRadarMaps([cloud], [(w, h)],
+                                                       map_size=_rect_map_size(self.img_size) if self.rect else 32))
 
     def infer(self, payload):
         """Device half (run_mp.py:296-330): input kernels, mode selection, ``Network.forward``, second NMS, rescale."""
@@ -129,8 +164,11 @@ def prepare_streams(frames, radar_frames, streams, img_size=416, pack=False, pix
     (``"bgr"`` ``[h,w,3]``, ``"yuyv"`` ``[h,w,2]``, ``"nv12"`` ``[h*3//2, w]``), their bytes are staged as they are and converted
     on the device; ``payload["hw"]`` is the picture's size.  ``None``: uint8 ``[h,w,3]`` RGB.
 
-    ``resize``: ``None`` / ``"nearest"`` or ``"area"`` (``StagedRaggedImages``); an unknown name raises here."""
+    ``resize``: ``None`` / ``"nearest"`` or ``"area"`` (``StagedRaggedImages``); an unknown name raises here.
+
+    ``img_size=(H, W)``: the frames are staged for the letterbox kernel (``StagedRaggedImages(size=(H, W))``)."""
     resize = resize_mode(resize, "prepare_streams")
+    img_size = _network_input_size(img_size, "prepare_streams")
     if len(frames) != streams or len(radar_frames) != streams:
         raise hip.MeError(f"MultiStreamFuser: {len(frames)} frames / {len(radar_frames)} radar lists for {streams} streams")
     frames = [torch.as_tensor(f) for f in frames]
@@ -200,22 +238,38 @@ class MultiStreamFuser:
     reference's scripts have no such option: ``"area"`` is pinned to torch's float64 ``area`` interpolation rounded to float32,
     not to the reference.  It needs ``max(h, w) <= 255 * img_size`` per frame, gives the nearest path's bits for ``max(h, w) ==
     img_size``, and leaves the geometry alone: box rescaling, the radar boxes and the tail do not change, and the auto mode's
-    mean is taken over the area-resized image.  Checked here, when the fuser is built."""
+    mean is taken over the area-resized image.  Checked here, when the fuser is built.
+
+    ``img_size=(H, W)`` (sides positive multiples of 32; ``(S, S)`` is ``S``): the rectangular network input.  Every frame is
+    letterboxed by one rule (``utils.utils.letterbox_geometry``) in the input launch (``me_image_batch_letterbox_u8_f32``), the
+    radar maps are the dataset's resized ``(H / 16, W / 16)`` maps (``me_radar_heatmap_rect_f32``; the raw 32 x 32 map of the
+    square path has no rectangular form), the network's radar boxes are rebuilt per axis from the device proposals
+    (``DeviceRadarProposals.letterbox_boxes``: two launches and one more small copy per step, for the counts the sub-batch
+    gather and ``info["radar_boxes"]`` use) and both tails rescale per axis - the tail kernel is unchanged, only its six
+    scalars per stream differ.  ``split="frame_modes"`` and ``resize="area"`` are refused with a rectangular size."""
 
     def __init__(self, model, calib_params, streams, model_mode=3, img_size=416, nms_iou=0.3, dark_threshold=0.08,
                  tail="device", split="forwards", pixel_format=None, resize=None, **generator_kwargs):
-        self.model, self.model_mode, self.img_size, self.streams = model, model_mode, img_size, int(streams)
+        self.model, self.model_mode, self.streams = model, model_mode, int(streams)
+        self.img_size = _network_input_size(img_size, "MultiStreamFuser")
+        self.rect = isinstance(self.img_size, tuple)
         self.nms_iou, self.dark_threshold = nms_iou, dark_threshold
         if tail not in ("device", "host"):
             raise hip.MeError(f"MultiStreamFuser: tail must be 'device' or 'host' (got {tail!r})")
         if split not in ("forwards", "frame_modes"):
             raise hip.MeError(f"MultiStreamFuser: split must be 'forwards' or 'frame_modes' (got {split!r})")
         self.split = split
+        if self.rect and split == "frame_modes":
+            raise hip.MeError(f"MultiStreamFuser: split='frame_modes' needs a square img_size (Network.forward refuses "
+                              f"frame_modes on {self.img_size[0]} x {self.img_size[1]} frames)")
         if self.streams <= 0:
             raise hip.MeError(f"MultiStreamFuser: streams must be positive (got {streams})")
         # None, one name or one per stream (prepare_streams checks the frames against it)
         self.pixel_format = None if pixel_format is None else pixel_format_names(pixel_format, self.streams, "stream")
         self.resize = resize_mode(resize, "MultiStreamFuser")
+        if self.rect and self.resize == "area":
+            raise hip.MeError(f"MultiStreamFuser: resize='area' has no rectangular form (img_size {self.img_size[0]} x "
+                              f"{self.img_size[1]})")
         self.tail = tail
         self.calib_params, self.generator_kwargs = calib_params, generator_kwargs
         self._device = getattr(model, "device", None)
@@ -276,8 +330,15 @@ class MultiStreamFuser:
         hws = payload["hw"]
         img = payload["img"].to(dev)
         step = self.generator.gen(payload["radar_frames"], hws)
-        radar_map = self.generator.heatmaps(32)   # the raw 32 x 32 maps, like FrameFuser (quirk q15)
         counts = step.host_counts
+        if self.rect:   # the resized maps and the per-axis boxes; column 4 becomes the rectangular canvas's count
+            radar_map = self.generator.heatmaps(_rect_map_size(self.img_size))
+            radar_box, box_counts = self.generator.letterbox_boxes(self.img_size)
+            counts = counts.copy()
+            counts[:, 4] = box_counts
+        else:
+            radar_map = self.generator.heatmaps(32)   # the raw 32 x 32 maps, like FrameFuser (quirk q15)
+            radar_box = step.radar_box
         if self.split == "frame_modes" and self.model_mode in (0, 1, 3):   # (a fixed mode 2 has no per-frame form: scalar call)
             per_stream, modes = self._infer_frame_modes(img, radar_map, step, hws)
             return self._results(per_stream, modes, counts)
@@ -288,12 +349,12 @@ class MultiStreamFuser:
             for mode in sorted(set(modes), key=lambda m: (m is None, m)):
                 idx = [s for s in range(n) if modes[s] == mode]
                 if len(idx) == n:
-                    rows = self.model(img, radar_map, step.radar_box, mode)
+                    rows = self.model(img, radar_map, radar_box, mode)
                 else:   # gather the sub-batch; the frame index column goes local and comes back as the stream number
                     where = torch.tensor(idx, dtype=torch.int64).to(dev)
                     box_rows = [r for s in idx for r in range(int(box_start[s]), int(box_start[s + 1]))]
                     local = [float(k) for k, s in enumerate(idx) for _ in range(int(counts[s, 4]))]
-                    rb = step.radar_box[torch.tensor(box_rows, dtype=torch.int64).to(dev)]
+                    rb = radar_box[torch.tensor(box_rows, dtype=torch.int64).to(dev)]
                     if len(local):
                         rb[:, 0] = torch.tensor(local, dtype=torch.float32).to(dev)
                     rows = self.model(img[where], radar_map[where], rb, mode)

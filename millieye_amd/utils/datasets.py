@@ -26,6 +26,7 @@ import torch
 from torch.utils.data import Dataset
 
 from .. import hip
+from .utils import canvas_hw, canvas_size
 
 __all__ = ["MyDataset", "StagedImages", "StagedRaggedImages", "StagedRadarMaps", "obtain_bboxs", "PIXEL_FORMATS",
            "picture_hw", "RESIZE_MODES", "resize_mode"]
@@ -188,18 +189,34 @@ class StagedRaggedImages(StagedImages):
     torch's float64 ``area`` interpolation of the padded ``u8 / 255`` square rounded to float32, which the kernel's integer
     arithmetic gives exactly (include/millieye_hip.h).  It needs ``max(h, w) <= 255 * size`` per frame (``pack()`` raises
     otherwise); with ``max(h, w) == size`` it gives the bits of the nearest path, and the geometry is the same, so box
-    rescaling does not change."""
+    rescaling does not change.
+
+    ``size=(H, W)``: the batch is ``[n,3,H,W]`` - every frame letterboxed by ``utils.utils.letterbox_geometry`` (padded with
+    zeros to the smallest rectangle of the canvas's aspect ratio that holds it, both axes may be padded, mirrored if asked) and
+    resized with one nearest ``F.interpolate(size=(H, W))`` by ``me_image_batch_letterbox_u8_f32``, always with the ``[n,5]``
+    descriptor (``formats=None``: all RGB).  The reference has no rectangular input; the result is torch's own
+    ``F.interpolate(F.pad(u8 / 255), size=(H, W), mode="nearest")`` bit for bit.  ``(S, S)`` is ``S``.  ``resize="area"`` with a
+    rectangular size raises :class:`hip.MeError` here: there is no rectangular area kernel."""
 
     packed = desc = None   # set by pack(): the frames' bytes in one uint8 buffer and the [n,4] ([n,5]) int64 descriptor
     formats = None         # None: packed RGB and the [n,4] descriptor; else one checked name per frame
     resize = None          # None / "nearest": the nearest kernels; "area": me_image_batch_area_u8_f32
+    rect = None            # (H, W) of a rectangular canvas: me_image_batch_letterbox_u8_f32
 
     def __init__(self, frames, size, flips=None, formats=None, resize=None):
-        super().__init__(frames, size, flips)
+        size = canvas_size(size, "StagedRaggedImages size")
+        self.rect = size if isinstance(size, tuple) else None   # (H, W) of a rectangular canvas
+        super().__init__(frames, size[0] if self.rect else size, flips)
         self.resize = resize_mode(resize, "StagedRaggedImages")
+        if self.rect:
+            if self.resize == "area":
+                raise hip.MeError(f"StagedRaggedImages: resize='area' has no rectangular form (size {self.rect[0]} x "
+                                  f"{self.rect[1]})")
+            self.size = self.rect
+            self.shape = torch.Size((len(self.frames), 3) + self.rect)
         if formats is not None:
             self.formats = pixel_format_names(formats, len(self.frames))
-        if formats is not None or self.resize == "area":
+        if formats is not None or self.resize == "area" or self.rect:
             self.frames = [torch.as_tensor(f) for f in self.frames]
 
     def _format_descriptor(self):
@@ -220,7 +237,7 @@ class StagedRaggedImages(StagedImages):
         their bytes into one buffer.  The object then carries ``packed`` / ``desc`` (through pickle too) and :meth:`to` only
         uploads them; ``keep_frames=False`` drops the per-frame tensors so that the bytes travel once."""
         n = len(self.frames)
-        if self.formats is not None or self.resize == "area":
+        if self.formats is not None or self.resize == "area" or self.rect:
             desc, total = self._format_descriptor()
         else:
             desc = torch.empty((n, 4), dtype=torch.int64)
@@ -257,6 +274,11 @@ class StagedRaggedImages(StagedImages):
         total = int(packed.numel())
         d_src = packed.to(device, non_blocking=True)
         d_desc = desc.pin_memory().to(device, non_blocking=True)
+        if self.rect:
+            hip.check(hip.lib().me_image_batch_letterbox_u8_f32(d_src.data_ptr(), total, d_desc.data_ptr(), n, out.data_ptr(),
+                                                                self.rect[0], self.rect[1], hip.stream_ptr()),
+                      "me_image_batch_letterbox_u8_f32")
+            return out
         if self.resize == "area":
             hip.check(hip.lib().me_image_batch_area_u8_f32(d_src.data_ptr(), total, d_desc.data_ptr(), n, out.data_ptr(),
                                                            self.size, hip.stream_ptr()), "me_image_batch_area_u8_f32")
@@ -281,12 +303,17 @@ class StagedRaggedImages(StagedImages):
 
 class StagedRadarMaps:
     """Radar points of a batch waiting for ``.to(device)``: per frame ``[n_i,4]`` float64 (u, v, depth, velocity) and
-    the original image size ``(w, h)``."""
+    the original image size ``(w, h)``.
+
+    ``map_size=(mh, mw)``: ``[n,3,mh,mw]`` maps for a rectangular network input (``me_radar_heatmap_rect_f32``): the same bins,
+    padded by ``utils.utils.letterbox_geometry`` to the aspect ratio of ``mh x mw`` and resized with bilinear
+    ``align_corners=True``.  This is the dataset's resized map, ``map_size = img_size / 16`` per side; the demos' raw 32 x 32
+    map (quirk q15) has no rectangular form.  ``(m, m)`` is ``m``."""
 
     def __init__(self, points, sizes, map_size, radar_maps_size=32):
         self.points, self.sizes = list(points), list(sizes)
-        self.map_size, self.radar_maps_size = int(map_size), int(radar_maps_size)
-        self.shape = torch.Size((len(self.points), 3, self.map_size, self.map_size))
+        self.map_size, self.radar_maps_size = canvas_size(map_size, "StagedRadarMaps map_size"), int(radar_maps_size)
+        self.shape = torch.Size((len(self.points), 3) + canvas_hw(self.map_size))
         self.dtype = torch.float32
 
     def __len__(self):
@@ -307,6 +334,11 @@ class StagedRadarMaps:
         d_pts = torch.from_numpy(np.ascontiguousarray(flat)).to(device)
         d_off = torch.from_numpy(offsets).to(device)
         d_sz = torch.tensor(self.sizes, dtype=torch.int32).reshape(n, 2).to(device)
+        if isinstance(self.map_size, tuple):
+            hip.check(hip.lib().me_radar_heatmap_rect_f32(d_pts.data_ptr(), d_off.data_ptr(), d_sz.data_ptr(), n,
+                                                          self.radar_maps_size, out.data_ptr(), self.map_size[0],
+                                                          self.map_size[1], hip.stream_ptr()), "me_radar_heatmap_rect_f32")
+            return out
         hip.check(hip.lib().me_radar_heatmap_f32(d_pts.data_ptr(), d_off.data_ptr(), d_sz.data_ptr(), n,
                                                  self.radar_maps_size, out.data_ptr(), self.map_size, hip.stream_ptr()),
                   "me_radar_heatmap_f32")

@@ -72,11 +72,55 @@ def weights_init_normal(m):
         nn.init.kaiming_normal_(m.weight)
 
 
+def canvas_size(size, what="img_size", multiple=1):
+    """A network input size as the caller gave it -> an ``int`` (square) or ``(H, W)`` with ``H != W``; ``(S, S)`` is ``S``.
+    Sides that are not positive multiples of ``multiple`` raise :class:`hip.MeError` naming the shape."""
+    if isinstance(size, (tuple, list)):
+        if len(size) != 2:
+            raise _hip.MeError(f"{what}: expected an int or (H, W), got {size!r}")
+        H, W = int(size[0]), int(size[1])
+        if H <= 0 or W <= 0 or H % multiple or W % multiple:
+            raise _hip.MeError(f"{what}: the sides of {H} x {W} must be positive multiples of {multiple}")
+        return H if H == W else (H, W)
+    return int(size)
+
+
+def canvas_hw(size):
+    """``(H, W)`` of an ``int`` or ``(H, W)`` network input size."""
+    return (int(size[0]), int(size[1])) if isinstance(size, (tuple, list)) else (int(size), int(size))
+
+
+def letterbox_geometry(picture_hw, canvas):
+    """The one geometry rule of the rectangular input path (include/millieye_hip.h): a picture ``(h, w)`` is padded with zeros
+    to ``(Ph, Pw)``, the smallest rectangle of the canvas's aspect ratio that holds it, and that is resized to the canvas
+    ``(H, W)`` in one ``F.interpolate``.  With ``g = gcd(H, W)``, ``a = H / g``, ``b = W / g``: ``k = max(ceil(h / a),
+    ceil(w / b))``, ``Ph = a k``, ``Pw = b k`` (so ``Ph / H == Pw / W`` exactly).  Returns ``(Ph, Pw, top, left)`` with
+    ``top = (Ph - h) // 2``, ``left = (Pw - w) // 2``; the remainder goes behind.  ``H == W`` is ``pad_to_square``."""
+    h, w = int(picture_hw[0]), int(picture_hw[1])
+    H, W = canvas_hw(canvas)
+    if h <= 0 or w <= 0 or H <= 0 or W <= 0:
+        raise _hip.MeError(f"letterbox_geometry: non-positive size in {h} x {w} -> {H} x {W}")
+    g = math.gcd(H, W)
+    a, b = H // g, W // g
+    k = max(-(-h // a), -(-w // b))
+    Ph, Pw = a * k, b * k
+    return Ph, Pw, (Ph - h) // 2, (Pw - w) // 2
+
+
 def rescale_terms(current_dim, original_shape):
     """Per axis the three python scalars of :func:`rescale_boxes`: ``{"x": (pad // 2, current_dim - pad, original), "y": ...}``
     (reference :41-56).  The one place they are computed: ``rescale_boxes`` applies them with torch, :func:`rescale_scalars`
-    hands them to ``me_stream_tail_f32``."""
+    hands them to ``me_stream_tail_f32``.
+
+    ``current_dim = (H, W)``: the canvas of :func:`letterbox_geometry`, per axis ``(pad // 2, canvas - pad, original)`` with
+    ``pad_x = (Pw - w) * (W / Pw)``, ``pad_y = (Ph - h) * (H / Ph)``; ``(S, S)`` gives the int form's python floats."""
     orig = {"y": original_shape[0], "x": original_shape[1]}
+    if isinstance(current_dim, (tuple, list)):
+        H, W = canvas_hw(current_dim)
+        Ph, Pw, _top, _left = letterbox_geometry(original_shape, (H, W))
+        pad = {"x": (Pw - orig["x"]) * (W / Pw), "y": (Ph - orig["y"]) * (H / Ph)}
+        canvas = {"x": W, "y": H}
+        return {axis: (pad[axis] // 2, canvas[axis] - pad[axis], orig[axis]) for axis in ("x", "y")}
     ratio = current_dim / max(original_shape)
     pad = {"x": max(orig["y"] - orig["x"], 0) * ratio, "y": max(orig["x"] - orig["y"], 0) * ratio}
     return {axis: (pad[axis] // 2, current_dim - pad[axis], orig[axis]) for axis in ("x", "y")}
@@ -84,7 +128,8 @@ def rescale_terms(current_dim, original_shape):
 
 def rescale_boxes(boxes, current_dim, original_shape):
     """Undo pad-to-square + resize (reference :41-56); mutates and returns ``boxes`` (xyxy in the square frame ->
-    xyxy in the original ``(h, w)`` frame).  Per axis: ``((v - pad // 2) / unpadded) * original``."""
+    xyxy in the original ``(h, w)`` frame).  Per axis: ``((v - pad // 2) / unpadded) * original``.  ``current_dim`` may be
+    a rectangular canvas ``(H, W)`` (:func:`rescale_terms`)."""
     terms = rescale_terms(current_dim, original_shape)
     for col, axis in ((0, "x"), (1, "y"), (2, "x"), (3, "y")):
         half_pad, unpadded, original = terms[axis]

@@ -28,7 +28,12 @@ python tools/multistream_latency.py --pixel-format rgb nv12 yuyv --streams 8 32 
 ``--resize nearest area`` prints only the comparison of the resize modes (:func:`compare_resize`; profiles/multistream_resize.txt):
 per network, S, frame size (``--frame-size H W``, repeatable) and pixel format the bytes a step packs, the input launch's own time,
 a device-to-device copy of the same packed buffer, the area launch's source-read rate as a fraction of that copy's, and the step:
-python tools/multistream_latency.py --resize nearest area --frame-size 480 640 --frame-size 1080 1920 --streams 8 32 --steps 20 --out profiles/multistream_resize.txt"""
+python tools/multistream_latency.py --resize nearest area --frame-size 480 640 --frame-size 1080 1920 --streams 8 32 --steps 20 --out profiles/multistream_resize.txt
+
+``--img-size H W`` (repeatable) prints only the comparison of network input sizes (:func:`compare_img_sizes`;
+profiles/letterbox_inference.txt): per network, S and frame size the input launch alone, the packed payload to the device batch, the
+radar-box rebuild with its count copy (rectangular sizes only), ``Network.forward`` alone and the whole step, every size in the same process, in rotating blocks:
+python tools/multistream_latency.py --img-size 416 416 --img-size 256 416 --frame-size 1080 1920 --streams 8 --steps 40 --nets yolov3-tiny-12:f32 yolov3:f32 yolov3:bf16 --out profiles/letterbox_inference.txt"""
 import argparse
 import os
 import statistics
@@ -251,6 +256,106 @@ def compare_resize(args, say):
                     del ring, spare, out
 
 
+def compare_img_sizes(args, say):
+    """``--img-size``: ``MultiStreamFuser(img_size=)`` for every size named, the first one (the square path) as the yardstick,
+    in one process and rotating blocks.  Every fuser sees the same dark RGB frames (``--frame-size``, default 1080 1920: one
+    fusion forward at batch S) and radar streams.
+
+    "launch": the input launch alone on buffers already on the device (HIP events around a block of back-to-back launches over a
+    ring of copies of the packed buffer, as in :func:`compare_resize`) - ``me_image_batch_pad_resize_flip_u8_f32`` for a square
+    size, ``me_image_batch_letterbox_u8_f32`` for a rectangular one.  "boxes": ``DeviceRadarProposals.letterbox_boxes`` - two
+    launches and the copy of S + 1 counts, the call a rectangular step adds (host time, it synchronises).  "to device": from the
+    packed payload to the batch on the device (the upload of the frames' bytes from pageable memory and the launch, device
+    synchronised around every block).  "forward": ``Network.forward`` in the fusion mode on the step's own inputs, HIP events.
+    "step": the whole in-process step from the caller's frames (packing into pinned memory, upload, radar chain, maps, boxes,
+    mode rule, forward, tail)."""
+    from millieye_amd import hip
+    sizes = [h if h == w else (h, w) for h, w in args.img_size]
+    frame_sizes = [tuple(v) for v in (args.frame_size or [[1080, 1920]])]
+    say(f"# {torch.cuda.get_device_name(0)}; dark rgb frames; {args.steps} steps (launches) per block, {args.repeats} blocks per size "
+        f"in rotating order, median (min .. max) of the blocks, 5 warm-up steps")
+    for cfg, dtype in args.nets:
+        net = _demo_net(cfg, dtype)
+        for n in args.streams:
+            radar = [[[radar_points((f + 7 * s) % 45)] for s in range(n)] for f in range(args.steps)]
+            for h, w in frame_sizes:
+                distinct = [dark_native_frame("rgb", s, h, w) for s in range(min(n, 4))]
+                frames = [distinct[s % len(distinct)] for s in range(n)]
+                fusers = [MultiStreamFuser(net, RADAR_CALIB, n, model_mode=3, min_hits=2, img_size=size) for size in sizes]
+                dev = fusers[0].device
+                lib, stream = hip.lib(), hip.stream_ptr()
+                staged = [fuser.prepare(frames, radar[0], pack=True)["img"] for fuser in fusers]
+                nbytes = int(staged[0].packed.numel())
+                ring = [staged[0].packed.to(dev) for _ in range(max(1, min(16, -(-(1 << 30) // nbytes))))]
+                descs = [st.desc.to(dev) for st in staged]
+                outs = [torch.empty(tuple(st.shape), device=dev, dtype=torch.float32) for st in staged]
+
+                def launches(i):
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    a.record()
+                    for f in range(args.steps):
+                        src = ring[f % len(ring)].data_ptr()
+                        if fusers[i].rect:
+                            H, W = sizes[i]
+                            hip.check(lib.me_image_batch_letterbox_u8_f32(src, nbytes, descs[i].data_ptr(), n, outs[i].data_ptr(),
+                                                                          H, W, stream), "me_image_batch_letterbox_u8_f32")
+                        else:
+                            hip.check(lib.me_image_batch_pad_resize_flip_u8_f32(src, nbytes, descs[i].data_ptr(), n,
+                                                                                outs[i].data_ptr(), sizes[i], stream),
+                                      "me_image_batch_pad_resize_flip_u8_f32")
+                    b.record()
+                    torch.cuda.synchronize()
+                    return a.elapsed_time(b) * 1e-3 / args.steps
+
+                inputs = []
+                for i, fuser in enumerate(fusers):
+                    for f in range(5):
+                        res = fuser(frames, radar[f])
+                    assert all(info["mode"] == 0 for _r, info in res)
+                    gen = fuser.generator
+                    if fuser.rect:
+                        inputs.append((staged[i].to(dev), gen.heatmaps((sizes[i][0] // 16, sizes[i][1] // 16)),
+                                       gen.letterbox_boxes(sizes[i])[0]))
+                    else:
+                        step = gen.gen(radar[5], [(h, w)] * n)
+                        inputs.append((staged[i].to(dev), gen.heatmaps(32), step.radar_box))
+                    launches(i)
+
+                def forwards(i):
+                    img, radar_map, radar_box = inputs[i]
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    a.record()
+                    with torch.no_grad():
+                        for f in range(args.steps):
+                            net(img, radar_map, radar_box.clone(), 0)
+                    b.record()
+                    torch.cuda.synchronize()
+                    return a.elapsed_time(b) * 1e-3 / args.steps
+
+                t_launch, t_fwd = [[] for _ in sizes], [[] for _ in sizes]
+                for r in range(args.repeats):
+                    for i in [(r + j) % len(sizes) for j in range(len(sizes))]:
+                        t_launch[i].append(launches(i))
+                        t_fwd[i].append(forwards(i))
+                t_step = timed_rotating([lambda f, i=i: fusers[i](frames, radar[f]) for i in range(len(sizes))], args.steps,
+                                        args.repeats)
+                t_up = timed_rotating([lambda f, i=i: staged[i].to(dev) for i in range(len(sizes))], args.steps, args.repeats)
+                for i, size in enumerate(sizes):
+                    name = f"{size[0]}x{size[1]}" if fusers[i].rect else f"{size}x{size}"
+                    line = (f"{cfg:16s} {dtype:4s} S={n:2d} {h}x{w} -> {name:9s}: {nbytes / 1e6:6.2f} MB/step | launch "
+                            f"{_spread(t_launch[i], 1e6)} us | to device {_spread(t_up[i])} ms | forward {_spread(t_fwd[i])} ms "
+                            f"(x {statistics.median(t_fwd[i]) / statistics.median(t_fwd[0]):5.3f}) | step {_spread(t_step[i])} ms "
+                            f"(x {statistics.median(t_step[i]) / statistics.median(t_step[0]):5.3f})")
+                    if fusers[i].rect:
+                        gen = fusers[i].generator
+                        t_box = timed_rotating([lambda f: gen.letterbox_boxes(sizes[i])], args.steps, args.repeats)[0]
+                        line += f" | boxes + count copy {_spread(t_box, 1e6)} us"
+                    say(line)
+                del ring, outs, inputs
+
+
 def timed_ab(fn_a, fn_b, steps, repeats=4):
     """``timed`` for two variants, a block of each per repeat in alternating order (A B, B A, ...), so that both see the same
     machine state and neither always runs first."""
@@ -364,7 +469,10 @@ def main():
                     help="only the comparison of these resize modes against the first one (compare_resize), for the formats of "
                          "--pixel-format (default rgb nv12)")
     ap.add_argument("--frame-size", nargs=2, type=int, action="append", metavar=("H", "W"), default=None,
-                    help="--resize: the frames' size (default 480 640); may be given several times")
+                    help="--resize / --img-size: the frames' size (default 480 640 / 1080 1920); may be given several times")
+    ap.add_argument("--img-size", nargs=2, type=int, action="append", metavar=("H", "W"), default=None,
+                    help="only the comparison of these network input sizes against the first one (compare_img_sizes); sides "
+                         "multiples of 32; may be given several times")
     args = ap.parse_args()
     args.nets = [tuple(v.split(":")) for v in args.nets]
     lines = []
@@ -374,6 +482,12 @@ def main():
         lines.append(text)
 
     say(f"# python tools/multistream_latency.py {' '.join(sys.argv[1:])}".rstrip())
+    if args.img_size:
+        compare_img_sizes(args, say)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return
     if args.resize:
         compare_resize(args, say)
         if args.out:
