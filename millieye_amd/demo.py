@@ -154,7 +154,7 @@ class FrameFuser:
                           points=payload["points"])
 
 
-def prepare_streams(frames, radar_frames, streams, img_size=416, pack=False, pixel_format=None, resize=None):
+def prepare_streams(frames, radar_frames, streams, img_size=416, pack=False, pixel_format=None, resize=None, out=None):
     """Host half of a :class:`MultiStreamFuser` step: checks and stages the raw frame bytes and radar frames (picklable; the
     trackers live on the device, so the radar chain itself belongs to ``infer``).  Needs neither a model nor the HIP library:
     ``pipeline.FusionPipeline`` calls it in the producer process with ``pack=True``, which also does the host loop of
@@ -166,7 +166,10 @@ def prepare_streams(frames, radar_frames, streams, img_size=416, pack=False, pix
 
     ``resize``: ``None`` / ``"nearest"`` or ``"area"`` (``StagedRaggedImages``); an unknown name raises here.
 
-    ``img_size=(H, W)``: the frames are staged for the letterbox kernel (``StagedRaggedImages(size=(H, W))``)."""
+    ``img_size=(H, W)``: the frames are staged for the letterbox kernel (``StagedRaggedImages(size=(H, W))``).
+
+    ``out`` (with ``pack=True``): the 1-D uint8 tensor the bytes are packed into (``StagedRaggedImages.pack(out=)``) - a slot of
+    the pipeline's ``handover.FrameRing``."""
     resize = resize_mode(resize, "prepare_streams")
     img_size = _network_input_size(img_size, "prepare_streams")
     if len(frames) != streams or len(radar_frames) != streams:
@@ -182,8 +185,10 @@ def prepare_streams(frames, radar_frames, streams, img_size=416, pack=False, pix
                 raise hip.MeError(f"stream {i}: frame must be uint8 [h,w,3] (got {frame.dtype} {tuple(frame.shape)})")
         hws = [(int(f.shape[0]), int(f.shape[1])) for f in frames]
         img = StagedRaggedImages(frames, img_size, resize=resize)
+    if out is not None and not pack:
+        raise hip.MeError("prepare_streams: out= needs pack=True")
     if pack:
-        img.pack(keep_frames=False)
+        img.pack(keep_frames=False, out=out)
     return dict(hw=hws, img=img, radar_frames=[list(r) for r in radar_frames])
 
 

@@ -20,6 +20,11 @@ travels with the packed frames.  The trackers live on the device, in the consume
 step (a dropped step would lose its radar frames and break the tracks): it blocks on the full queue, and the consumer skips
 instead - it takes everything that waits, runs ``advance`` (the radar chain alone) on all but the newest step, in order, and
 ``infer`` on the newest.
+
+``handover="pinned"`` (opt-in, multi-stream only): the frames' bytes do not travel through the queue but through a
+``handover.FrameRing`` - one shared-memory segment this process creates, registers with the HIP runtime once and unlinks; the
+producer packs into a free slot and queues the slot's index, the consumer uploads out of the registered pages and gives the
+index back (:class:`FusionPipeline`).
 """
 import multiprocessing as mp
 import pickle
@@ -34,6 +39,7 @@ class ProducerError(RuntimeError):
     """The producer process failed (source iterator, radar tracking, staging); carries its traceback text."""
 
 QUEUE_SIZE = 3      # run_mp.py:289
+HANDOVERS = ("pinned",)
 _END = "__end__"
 
 
@@ -64,22 +70,128 @@ def _producer(q, first_done, all_done, source_factory, prepare_factory, drop_old
         all_done.wait(timeout=120)
 
 
-def _producer_multi(q, first_done, all_done, source_factory, prepare_factory):
-    """The producer of a multi-stream pipeline: every step is queued (blocking ``put``), skipping is the consumer's business."""
+class _ConsumerLeft(Exception):
+    """The producer's polls found ``all_done`` set: nobody will take another step."""
+
+
+def _poll(source_q, all_done, poll_s=0.2):
+    """``source_q.get()`` that gives up once the consumer has left (a blocked ``get`` would outlive it)."""
+    while True:
+        try:
+            return source_q.get(timeout=poll_s)
+        except _queue.Empty:
+            if all_done.is_set():
+                raise _ConsumerLeft() from None
+
+
+def _producer_multi(q, first_done, all_done, source_factory, prepare_factory, handover=None):
+    """The producer of a multi-stream pipeline: every step is queued (blocking ``put``), skipping is the consumer's business.
+
+    ``handover``: ``None`` or ``(ring, free, ctrl)`` - the consumer's ``handover.FrameRing`` (attached here by unpickling; ``None``:
+    it arrives over ``ctrl`` behind the first-frame rendezvous, sized from step 0), the queue of free slot indices and the
+    control queue.  With a ring, a step takes a free slot before it packs (polling, so that a consumer that left is noticed),
+    packs into it and queues the payload without the bytes; a step that does not fit gives the slot back unused and travels
+    through the queue like any step without a ring."""
     error = None
+    ring = None
     try:
         prepare = prepare_factory()
+        if handover is not None:
+            from .utils.datasets import PackBufferTooSmall
+            ring, free, ctrl = handover
         for idx, (frames, radar_frames) in enumerate(source_factory()):
-            payload = prepare(frames, radar_frames)
+            payload = None
+            if ring is not None:
+                slot = _poll(free, all_done)
+                try:
+                    payload = prepare(frames, radar_frames, out=ring.slot(slot))
+                    payload["img"].lend_to_ring(slot)
+                except PackBufferTooSmall:
+                    free.put(slot)
+                    payload = prepare(frames, radar_frames)
+                    payload["handover_fallback"] = True
+            if payload is None:
+                payload = prepare(frames, radar_frames)
             payload["frame_idx"] = idx
             q.put(payload)
             if idx == 0:
                 first_done.wait()
+                if handover is not None and ring is None:
+                    ring = _poll(ctrl, all_done)
+    except _ConsumerLeft:
+        pass
     except BaseException as exc:
         error = f"{type(exc).__name__}: {exc}\n{traceback.format_exc()}"
     finally:
         q.put({"frame_idx": _END, "dropped": 0, "error": error})
         all_done.wait(timeout=120)
+        if ring is not None:
+            payload = None   # (its img may still view a slot)
+            ring.close()
+
+
+class _Handover:
+    """The consumer's side of ``handover="pinned"``: the ring (owned and registered here), the queue of free slot indices, the
+    control queue that carries the ring's handle when step 0 sizes it, and the staged objects currently bound to a slot."""
+
+    def __init__(self, ctx, ring_slots):
+        self.ring, self.ring_slots, self.fallback = None, ring_slots, 0
+        self.free, self.ctrl = ctx.Queue(), ctx.Queue()
+        self.bound = []
+
+    @property
+    def slot_bytes(self):
+        return None if self.ring is None else self.ring.slot_bytes
+
+    def open(self, slot_bytes):
+        from .handover import FrameRing
+        self.ring = FrameRing(self.ring_slots, slot_bytes)
+        self.ring.register()
+        for i in range(self.ring_slots):
+            self.free.put(i)
+
+    def open_for(self, payload):
+        """Size the ring from a step that came through the queue - its byte total plus one quarter - and send the producer
+        the handle."""
+        packed = getattr(payload.get("img"), "packed", None)
+        if packed is None:
+            raise ValueError("FusionPipeline(handover='pinned', slot_bytes=None): step 0 carries no packed frames to size the "
+                             "ring from; pass slot_bytes=")
+        total = max(int(packed.numel()), 1)
+        self.open(total + total // 4)
+        self.ctrl.put(self.ring)     # (pickles to the handle)
+
+    def take(self, payload):
+        """A payload fresh from the queue: bind its frames to this process's mapping of the ring, or count the fallback."""
+        if payload.get("handover_fallback"):
+            self.fallback += 1
+            return
+        img = payload.get("img")
+        if getattr(img, "ring_slot", None) is not None:
+            img.bind(self.ring)
+            self.bound.append(img)
+
+    def give_back(self, payload, synchronize=False):
+        img = payload.get("img")
+        if not any(img is b for b in self.bound):
+            return
+        if synchronize:   # the upload out of the slot was queued on the current stream; infer= overrides need not end in a read
+            import torch
+            if torch.cuda.is_available() and torch.cuda.is_initialized():
+                torch.cuda.current_stream().synchronize()
+        self.bound = [b for b in self.bound if b is not img]
+        img.unbind()
+        self.free.put(img.ring_slot)
+
+    def close(self):
+        for img in self.bound:
+            img.unbind()
+        self.bound = []
+        if self.ring is not None:
+            self.ring.close()
+        for chan in (self.free, self.ctrl):
+            chan.cancel_join_thread()
+            chan.close()
 
 
 class _MultiPrepareFactory:
@@ -129,13 +241,41 @@ class FusionPipeline:
     the steps that were only advanced since the previous yield.  The source yields ``(frames, radar_frames)`` with S entries
     each.  ``skip_to_newest=True`` (default): of the steps that wait, all but the newest only run ``advance`` (the radar
     chain, so the trackers see every step in order); ``False``: every step is inferred.  ``stats["dropped"]`` counts the
-    skipped steps.  ``drop_oldest`` does not apply: the producer never drops.  ``advance``: override (tests)."""
+    skipped steps.  ``drop_oldest`` does not apply: the producer never drops.  ``advance``: override (tests).
+
+    ``handover="pinned"`` (multi-stream fusers only; default ``None``: every step's bytes travel through the queue): the frames'
+    bytes cross the process boundary in a :class:`millieye_amd.handover.FrameRing` - ``ring_slots`` (default ``QUEUE_SIZE + 2``,
+    at least 2) slots of ``slot_bytes`` in one shared-memory segment that this process creates, registers with the HIP runtime
+    once and unlinks when the iteration ends, however it ends.  The producer takes a free slot index from a queue before it
+    packs, packs straight into the slot and queues the payload without the bytes; the consumer uploads out of the registered
+    pages and gives the index back - for a step that was only advanced right after ``advance``, for the inferred step once
+    ``infer`` has returned and the current stream is synchronised.  The free-slot queue is the back-pressure; the producer
+    still never drops a step.  ``slot_bytes=None``: step 0 travels through the queue, the ring is sized from its byte total
+    plus one quarter and its handle reaches the producer at the first-frame rendezvous.  A later step that does not fit a slot
+    travels through the queue (``stats["handover_fallback"]`` counts them).  ``stats`` also holds ``handover``,
+    ``ring_slots`` and ``slot_bytes`` (``None`` when no ring was ever opened)."""
 
     def __init__(self, fuser, source_factory, infer=None, drop_oldest=True, prepare_factory=None, start_method="spawn",
-                 skip_to_newest=True, advance=None):
+                 skip_to_newest=True, advance=None, handover=None, ring_slots=None, slot_bytes=None):
         self.fuser, self.source_factory, self.drop_oldest = fuser, source_factory, drop_oldest
         self.infer = infer or fuser.infer
         self.multi = hasattr(fuser, "streams") and hasattr(fuser, "advance")
+        if handover is not None:
+            if handover not in HANDOVERS:
+                raise ValueError(f"FusionPipeline: unknown handover {handover!r} (None or one of {', '.join(HANDOVERS)})")
+            if not self.multi:
+                raise ValueError("FusionPipeline: handover= is for multi-stream fusers (a FrameFuser's frame is queued as it is)")
+            ring_slots = QUEUE_SIZE + 2 if ring_slots is None else int(ring_slots)
+            if ring_slots < 2:
+                raise ValueError(f"FusionPipeline: ring_slots must be at least 2 (got {ring_slots}): one slot is packed while "
+                                 f"another is read")
+            if slot_bytes is not None and int(slot_bytes) <= 0:
+                raise ValueError(f"FusionPipeline: slot_bytes must be positive (got {slot_bytes})")
+        elif ring_slots is not None or slot_bytes is not None:
+            raise ValueError("FusionPipeline: ring_slots= / slot_bytes= need handover='pinned'")
+        self.handover, self.ring_slots = handover, ring_slots
+        self.slot_bytes = None if slot_bytes is None else int(slot_bytes)
+        self.ring_name = None
         self.skip_to_newest = skip_to_newest
         self.advance = advance or getattr(fuser, "advance", None)
         if prepare_factory is None and self.multi:
@@ -181,12 +321,18 @@ class FusionPipeline:
         q = ctx.Queue(maxsize=QUEUE_SIZE)
         first_done = ctx.Event()
         all_done = ctx.Event()
-        proc = ctx.Process(target=_producer_multi, args=(q, first_done, all_done, self.source_factory, self.prepare_factory),
-                           daemon=True)
-        proc.start()
+        args = (q, first_done, all_done, self.source_factory, self.prepare_factory)
+        hand = None
+        if self.handover is not None:
+            hand = _Handover(ctx, self.ring_slots)
+            if self.slot_bytes is not None:
+                hand.open(self.slot_bytes)       # the ring exists before the producer starts
+            args += ((hand.ring, hand.free, hand.ctrl),)
         t0, frames, dropped = time.perf_counter(), 0, 0
-        end = None
+        end = proc = None
         try:
+            proc = ctx.Process(target=_producer_multi, args=args, daemon=True)
+            proc.start()
             while end is None:
                 waiting = [self._next_payload(q, proc)]
                 while self.skip_to_newest and waiting[-1]["frame_idx"] != _END:   # everything else that waits, in order
@@ -196,13 +342,22 @@ class FusionPipeline:
                         break
                 if waiting[-1]["frame_idx"] == _END:
                     end = waiting.pop()
+                if hand is not None:
+                    for payload in waiting:
+                        hand.take(payload)
                 skipped = []
                 for payload in waiting[:-1]:
                     self.advance(payload)
+                    if hand is not None:
+                        hand.give_back(payload)          # the radar chain does not read frames
                     skipped.append(payload["frame_idx"])
                 dropped += len(skipped)
                 if waiting:
                     results = self.infer(waiting[-1])
+                    if hand is not None:
+                        hand.give_back(waiting[-1], synchronize=True)
+                        if hand.ring is None:            # slot_bytes=None: step 0 came through the queue and sizes the ring
+                            hand.open_for(waiting[-1])
                     first_done.set()
                     frames += 1
                     yield results, dict(frame_idx=waiting[-1]["frame_idx"], skipped=skipped)
@@ -211,12 +366,19 @@ class FusionPipeline:
         finally:
             first_done.set()
             all_done.set()
-            if end is None:
-                proc.terminate()   # left early (break, an exception in infer): the producer may be blocked on the full queue
-            proc.join(timeout=10)
-            if proc.is_alive():
-                proc.terminate()
+            if proc is not None:
+                if end is None:
+                    proc.terminate()   # left early (break, an exception in infer): the producer may be blocked on the full queue
+                proc.join(timeout=10)
+                if proc.is_alive():
+                    proc.terminate()
             self.stats = dict(dropped=dropped, frames=frames, seconds=time.perf_counter() - t0)
+            if hand is not None:
+                self.stats.update(handover=self.handover, ring_slots=self.ring_slots, slot_bytes=hand.slot_bytes,
+                                  handover_fallback=hand.fallback)
+                self.ring_name = None if hand.ring is None else hand.ring.name   # (of the last run; gone by now)
+                waiting = payload = None
+                hand.close()          # after the producer is gone: unregister, unmap, unlink
 
     def __iter__(self):
         if self.multi:

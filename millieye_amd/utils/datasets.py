@@ -171,6 +171,10 @@ def resize_mode(resize, what="resize"):
     return resize
 
 
+class PackBufferTooSmall(hip.MeError):
+    """``StagedRaggedImages.pack(out=)``: the frames' bytes do not fit ``out`` (the message names both counts)."""
+
+
 class StagedRaggedImages(StagedImages):
     """A ``StagedImages`` whose ``.to(device)`` builds the whole batch in one launch: every frame's bytes are packed into one
     pinned uint8 buffer and uploaded once, with a ``[n,4]`` int64 descriptor ``(byte offset, h, w, flip)`` per frame, and
@@ -202,6 +206,8 @@ class StagedRaggedImages(StagedImages):
     formats = None         # None: packed RGB and the [n,4] descriptor; else one checked name per frame
     resize = None          # None / "nearest": the nearest kernels; "area": me_image_batch_area_u8_f32
     rect = None            # (H, W) of a rectangular canvas: me_image_batch_letterbox_u8_f32
+    ring_slot = None       # set by lend_to_ring(): ``packed`` lies in this slot of a handover.FrameRing and does not pickle
+    ring_total = 0         # ... and holds this many bytes
 
     def __init__(self, frames, size, flips=None, formats=None, resize=None):
         size = canvas_size(size, "StagedRaggedImages size")
@@ -232,10 +238,14 @@ class StagedRaggedImages(StagedImages):
             total += frame.numel()
         return desc, total
 
-    def pack(self, pin=False, keep_frames=True):
+    def pack(self, pin=False, keep_frames=True, out=None):
         """The host half of :meth:`to`, callable ahead of time and without a GPU (``pin=False``): checks the frames and copies
         their bytes into one buffer.  The object then carries ``packed`` / ``desc`` (through pickle too) and :meth:`to` only
-        uploads them; ``keep_frames=False`` drops the per-frame tensors so that the bytes travel once."""
+        uploads them; ``keep_frames=False`` drops the per-frame tensors so that the bytes travel once.
+
+        ``out``: a 1-D contiguous uint8 CPU tensor the bytes go straight into - a slot of a ``handover.FrameRing`` - instead of a
+        fresh buffer; ``packed`` is ``out[:total]`` and the bytes behind ``total`` are not touched.  A too-small ``out`` raises
+        :class:`PackBufferTooSmall` (a :class:`hip.MeError`) after all the checks and before a byte is written."""
         n = len(self.frames)
         if self.formats is not None or self.resize == "area" or self.rect:
             desc, total = self._format_descriptor()
@@ -248,7 +258,17 @@ class StagedRaggedImages(StagedImages):
                     raise hip.MeError(f"frame {i}: expected uint8 [h,w,3], got {frame.dtype} {tuple(frame.shape)}")
                 desc[i, 0], desc[i, 1], desc[i, 2], desc[i, 3] = total, h, w, int(self.flips[i])
                 total += h * w * 3
-        packed = torch.empty((total,), dtype=torch.uint8, pin_memory=pin)
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 1 or out.device.type != "cpu" \
+                    or not out.is_contiguous():
+                raise hip.MeError("StagedRaggedImages.pack(out=): a 1-D contiguous uint8 CPU tensor is expected (got "
+                                  f"{getattr(out, 'dtype', type(out).__name__)} {tuple(getattr(out, 'shape', ()))})")
+            if int(out.numel()) < total:
+                raise PackBufferTooSmall(f"StagedRaggedImages.pack(out=): the frames hold {total} bytes, out holds "
+                                         f"{int(out.numel())}")
+            packed = out[:total]
+        else:
+            packed = torch.empty((total,), dtype=torch.uint8, pin_memory=pin)
         for i, frame in enumerate(self.frames):
             start = int(desc[i, 0])
             packed[start:start + frame.numel()].copy_(frame.reshape(-1))
@@ -257,6 +277,37 @@ class StagedRaggedImages(StagedImages):
             self.frames = []
         return self
 
+    # A packed object whose bytes lie in slot ``ring_slot`` of a ``handover.FrameRing`` (``lend_to_ring``, after
+    # ``pack(out=ring.slot(i))``) pickles without them: the slot index and the byte total travel, and the receiver binds the
+    # object to its own mapping of the same ring (``bind``) before ``to()``.  Any other object pickles as it always did.
+    def lend_to_ring(self, slot):
+        if self.packed is None:
+            raise hip.MeError("StagedRaggedImages.lend_to_ring(): pack(out=ring.slot(i)) first")
+        self.ring_slot, self.ring_total = int(slot), int(self.packed.numel())
+        return self
+
+    def bind(self, ring):
+        if self.ring_slot is None:
+            raise hip.MeError("StagedRaggedImages.bind(): the object's bytes do not lie in a ring")
+        slot = ring.slot(self.ring_slot)
+        if self.ring_total > int(slot.numel()):
+            raise hip.MeError(f"StagedRaggedImages.bind(): {self.ring_total} bytes in a slot of {int(slot.numel())}")
+        self.packed = slot[:self.ring_total]
+        return self
+
+    def unbind(self):
+        """Forget the slot's bytes (the slot is about to be given back); ``to()`` then raises until the next ``bind``."""
+        if self.ring_slot is not None:
+            self.packed = None
+        return self
+
+    def __getstate__(self):
+        if self.ring_slot is None:
+            return self.__dict__
+        state = dict(self.__dict__)
+        state["packed"] = None
+        return state
+
     def __len__(self):
         return int(self.shape[0])
 
@@ -264,6 +315,8 @@ class StagedRaggedImages(StagedImages):
         device = torch.device(device)
         if device.type != "cuda":
             raise hip.MeError("StagedRaggedImages.to(): the batch is assembled by the HIP library - CUDA device required")
+        if self.packed is None and self.ring_slot is not None:
+            raise hip.MeError(f"StagedRaggedImages.to(): the bytes lie in slot {self.ring_slot} of a FrameRing - bind(ring) first")
         n = int(self.shape[0])
         out = torch.empty(tuple(self.shape), device=device, dtype=torch.float32)
         if n == 0:

@@ -33,7 +33,12 @@ python tools/multistream_latency.py --resize nearest area --frame-size 480 640 -
 ``--img-size H W`` (repeatable) prints only the comparison of network input sizes (:func:`compare_img_sizes`;
 profiles/letterbox_inference.txt): per network, S and frame size the input launch alone, the packed payload to the device batch, the
 radar-box rebuild with its count copy (rectangular sizes only), ``Network.forward`` alone and the whole step, every size in the same process, in rotating blocks:
-python tools/multistream_latency.py --img-size 416 416 --img-size 256 416 --frame-size 1080 1920 --streams 8 --steps 40 --nets yolov3-tiny-12:f32 yolov3:f32 yolov3:bf16 --out profiles/letterbox_inference.txt"""
+python tools/multistream_latency.py --img-size 416 416 --img-size 256 416 --frame-size 1080 1920 --streams 8 --steps 40 --nets yolov3-tiny-12:f32 yolov3:f32 yolov3:bf16 --out profiles/letterbox_inference.txt
+
+``--handover queue pinned`` prints only the comparison of the pipeline's hand-overs (:func:`compare_handover`;
+profiles/multistream_handover.txt): per network, S, frame size and pixel format the pipeline's steps/s through the queue and through
+the pinned ring, two passes each in opposite order, the in-process fuser's steps/s, the ratios, and where a consumer step goes:
+python tools/multistream_latency.py --handover queue pinned --streams 8 32 --out profiles/multistream_handover.txt"""
 import argparse
 import os
 import statistics
@@ -168,6 +173,141 @@ def compare_formats(args, say):
                     line += (f" | pipeline {', '.join(f'{v:6.1f}' for v in pipe[fmt])} steps/s, ratio to the in-process step "
                              f"{', '.join(f'{v * med_step:4.2f}' for v in pipe[fmt])} (x {best / max(pipe[fmts[0]]):4.2f} of {fmts[0]})")
                 say(line)
+
+
+def handover_frames(fmt, n, hw):
+    """``n`` dark ``hw`` frames in ``fmt`` for :func:`compare_handover`: four distinct pictures, repeated over the streams (the
+    bytes are copied per stream all the same; generating 32 distinct 1080p frames would take longer than the run)."""
+    base = [dark_native_frame(fmt, s, *hw) for s in range(min(n, 4))]
+    return [base[s % len(base)] for s in range(n)]
+
+
+class HandoverSource:
+    """Picklable source of :func:`compare_handover`: ``steps`` steps of :func:`handover_frames`."""
+
+    def __init__(self, steps, n, fmt, hw):
+        self.steps, self.n, self.fmt, self.hw = steps, n, fmt, tuple(hw)
+
+    def __call__(self):
+        frames = handover_frames(self.fmt, self.n, self.hw)
+        for f in range(self.steps):
+            yield frames, [[radar_points((f + 7 * s) % 45)] for s in range(self.n)]
+
+
+class _PhasedInfer:
+    """``infer=`` of a measured pipeline run: ``fuser.infer`` with three clocks and no added synchronisation.  Per step: the
+    time since the previous ``infer`` returned (the slot's return, the caller's loop and the wait for the next payload), the host
+    time inside ``payload["img"].to()`` with the device time between two events around it (the upload and the input launch), and
+    the rest of ``infer``."""
+
+    def __init__(self, fuser):
+        self.fuser, self.rows, self.last = fuser, [], None
+        self.events = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+
+    def __call__(self, payload):
+        t0 = time.perf_counter()
+        wait = None if self.last is None else t0 - self.last
+        img, rec = payload["img"], {}
+        e0, e1 = self.events
+
+        def to(device, *a, **k):
+            e0.record()
+            a0 = time.perf_counter()
+            out = type(img).to(img, device, *a, **k)
+            rec["host"] = time.perf_counter() - a0
+            e1.record()
+            return out
+        img.to = to
+        try:
+            results = self.fuser.infer(payload)
+        finally:
+            del img.to
+        t1 = time.perf_counter()
+        e1.synchronize()
+        if wait is not None:     # (the first step - spawn, rendezvous, plans - is left out)
+            self.rows.append((wait, rec["host"], e0.elapsed_time(e1) * 1e-3, t1 - t0 - rec["host"]))
+        self.last = time.perf_counter()
+        return results
+
+    def medians(self):
+        return [statistics.median(col) * 1e3 for col in zip(*self.rows)]
+
+
+def compare_handover(args, say):
+    """``--handover queue pinned``: the two hand-overs of ``FusionPipeline`` - ``queue``: ``handover=None``, every step's bytes
+    through the queue's shared memory and up from pageable memory; ``pinned``: ``handover="pinned"``, the bytes packed into a
+    registered ``handover.FrameRing`` slot and up from there - against each other and against the in-process fuser.  Per
+    network, S, frame size (``--frame-size``, repeatable) and pixel format: dark frames (one forward at batch S), every step
+    inferred, two passes per mode in opposite order, steps/s of each from the first step's result (spawn, rendezvous: left out) to
+    the last one's - "with the teardown": to the end of the iteration, which adds the producer's exit (a fixed 0.5 - 1 s per run,
+    a third of a 100-step run; the two-process rows of the other modes of this tool include it); the
+    in-process fuser's steps/s (median of ``REPEATS`` blocks) and every pass's ratio to it; "bar": the gain of ``pinned`` over
+    ``queue`` (means of the passes) against the larger pass-to-pass spread of the two modes.  The second line of a row holds
+    per mode the medians over the consumer's steps of both passes of the phases of :class:`_PhasedInfer`."""
+    from millieye_amd.handover import FrameRing
+    from millieye_amd.pipeline import FusionPipeline
+    modes = args.handover
+    sizes = [tuple(v) for v in (args.frame_size or [(480, 640), (1080, 1920)])]
+    fmts = args.pixel_format or ["rgb", "nv12"]
+    say(f"# {torch.cuda.get_device_name(0)}; dark frames; pipeline: {args.steps} steps per run, every step inferred, timed from the "
+        f"first step's result to the last one's, two passes per hand-over in opposite order; in-process: {args.steps} steps per block, median of {REPEATS} blocks, "
+        f"5 warm-up steps")
+    probe = FrameRing(2, 1 << 20)
+    status = probe.register()
+    say(f"# hipHostRegister of a 2 x 1 MiB ring: status {status}; torch reports slot.is_pinned() = {probe.slot(1).is_pinned()}")
+    probe.close()
+    for cfg, dtype in args.nets:
+        net = _demo_net(cfg, dtype)
+        for n in args.streams:
+            for hw in sizes:
+                for fmt in fmts:
+                    radar = [[[radar_points((f + 7 * s) % 45)] for s in range(n)] for f in range(args.steps)]
+                    frames = handover_frames(fmt, n, hw)
+                    pixfmt = None if fmt == "rgb" else fmt      # (rgb: the default path, the one the earlier pipeline rows ran)
+                    local = MultiStreamFuser(net, RADAR_CALIB, n, model_mode=3, min_hits=2, pixel_format=pixfmt)
+                    for f in range(5):
+                        out = local(frames, radar[f])
+                    assert all(info["mode"] == 0 for _r, info in out)
+                    t_local = timed(lambda f: local(frames, radar[f]), args.steps)
+                    nbytes = int(local.prepare(frames, radar[0], pack=True)["img"].packed.numel())
+                    rate, whole, phases, stats = {m: [] for m in modes}, {m: [] for m in modes}, {}, {}
+                    for order in (modes, modes[::-1]):
+                        for mode in order:
+                            piped = MultiStreamFuser(net, RADAR_CALIB, n, model_mode=3, min_hits=2, pixel_format=pixfmt)
+                            infer = phases.setdefault(mode, _PhasedInfer(piped))
+                            infer.fuser, infer.last = piped, None
+                            pipe = FusionPipeline(piped, HandoverSource(args.steps + 1, n, fmt, hw), infer=infer,
+                                                  skip_to_newest=False, handover=None if mode == "queue" else mode)
+                            t0, done = None, 0
+                            for _results, _info in pipe:
+                                if t0 is None:
+                                    torch.cuda.synchronize()
+                                    t0 = time.perf_counter()
+                                else:
+                                    done += 1
+                                    t_last = time.perf_counter()
+                            rate[mode].append(done / (t_last - t0))
+                            whole[mode].append(done / (time.perf_counter() - t0))
+                            stats[mode] = pipe.stats
+                    head = f"{cfg:16s} {dtype:4s} S={n:2d} {hw[0]:4d}x{hw[1]:<4d} {fmt:4s}"
+                    line = f"{head}: {nbytes / 1e6:7.2f} MB/step | in-process {1 / t_local:6.1f} steps/s"
+                    for mode in modes:
+                        line += (f" | {mode} {', '.join(f'{v:6.1f}' for v in rate[mode])} steps/s (x "
+                                 f"{', '.join(f'{v * t_local:4.2f}' for v in rate[mode])} of in-process; with the teardown "
+                                 f"{', '.join(f'{v:5.1f}' for v in whole[mode])})")
+                    if "queue" in rate and "pinned" in rate:
+                        mean = {m: statistics.mean(rate[m]) for m in modes}
+                        spread = max(max(rate[m]) - min(rate[m]) for m in modes)
+                        gain = mean["pinned"] - mean["queue"]
+                        line += (f" | pinned / queue x {mean['pinned'] / mean['queue']:4.2f}; bar: gain {gain:+6.1f} steps/s against "
+                                 f"a spread of {spread:5.1f}: {'cleared' if gain > spread else 'NOT cleared'}")
+                        fallback = stats["pinned"].get("handover_fallback")
+                        if fallback:
+                            line += f" ({fallback} steps fell back to the queue)"
+                    say(line)
+                    say(f"{head}: per consumer step, median ms: " + " | ".join(
+                        "{} wait {:6.2f}, to() host {:6.2f} / device {:6.2f}, rest of infer {:6.2f}".format(m, *phases[m].medians())
+                        for m in modes))
 
 
 def compare_resize(args, say):
@@ -473,6 +613,9 @@ def main():
     ap.add_argument("--img-size", nargs=2, type=int, action="append", metavar=("H", "W"), default=None,
                     help="only the comparison of these network input sizes against the first one (compare_img_sizes); sides "
                          "multiples of 32; may be given several times")
+    ap.add_argument("--handover", nargs="+", default=None, choices=["queue", "pinned"],
+                    help="only the comparison of these FusionPipeline hand-overs (compare_handover), for the sizes of --frame-size "
+                         "(default 480 640 and 1080 1920) and the formats of --pixel-format (default rgb nv12)")
     args = ap.parse_args()
     args.nets = [tuple(v.split(":")) for v in args.nets]
     lines = []
@@ -482,6 +625,12 @@ def main():
         lines.append(text)
 
     say(f"# python tools/multistream_latency.py {' '.join(sys.argv[1:])}".rstrip())
+    if args.handover:
+        compare_handover(args, say)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return
     if args.img_size:
         compare_img_sizes(args, say)
         if args.out:
