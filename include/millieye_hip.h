@@ -584,6 +584,35 @@ int me_conv_wgrad_mfma_f32(const float* x, int64_t x_pitch, const float* dy, int
 int me_conv_wgrad_mfma_oihw_f32(const float* x, int64_t x_pitch, const float* dy, int64_t dy_pitch, float* dw, int32_t n,
                                 int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t ksize, int32_t stride, int32_t pad,
                                 void* workspace, int64_t workspace_bytes, void* stream);
+/* me_conv_wgrad_form - which kernel one call of me_conv_wgrad_mfma_f32 (oihw == 0) / me_conv_wgrad_mfma_oihw_f32 (oihw != 0) with
+ * these arguments runs: the launcher itself decides through this function.  Returns ME_WGRAD_FORM_*, or the negative ME_E_* code
+ * the call would return before any launch; *splits (may be NULL) = the slabs of partial sums the reduction adds (1 with
+ * ME_WGRAD_REDUCE_NONE: the kernel writes dw itself), *reduce (may be NULL) = ME_WGRAD_REDUCE_*.  The pointers are only tested
+ * (NULL, 16-byte alignment), never read; no HIP call is made, so the query works on a machine without a GPU.  The process
+ * switches MILLIEYE_WGRAD_TILE / _DEPTH / _WGS / _MINPX, MILLIEYE_WGRAD9 / _NG / _WGS are read once, as in the launcher. */
+#define ME_WGRAD_FORM_STEM 1          /* stem_wgrad_kernel: cin == 3, 3x3, cout % 4 == 0, a workspace of 768 partials      */
+#define ME_WGRAD_FORM_NINE_TAP 2      /* conv_wgrad9_kernel<2,2,2>: 3x3 / stride 1 / pad 1, cin and cout % 64 == 0          */
+#define ME_WGRAD_FORM_NINE_TAP_4W 3   /* conv_wgrad9_kernel<2,2,1>: the same on four waves (MILLIEYE_WGRAD9_NG=1)           */
+#define ME_WGRAD_FORM_PIPE_64_32 4    /* conv_wgrad_pipe_kernel<64,32,4>: cin <= 32                                         */
+#define ME_WGRAD_FORM_PIPE_128_128 5  /* conv_wgrad_pipe_kernel<..,4> on the full-width tiles: MILLIEYE_WGRAD_DEPTH >= 5    */
+#define ME_WGRAD_FORM_PIPE_128_64 6
+#define ME_WGRAD_FORM_PIPE_64_128 7
+#define ME_WGRAD_FORM_PIPE_64_64 8
+#define ME_WGRAD_FORM_TILE_128_128 9  /* conv_wgrad_tile_kernel<128,128>: k >= 3, 16384 pixels or more, cin, cout >= 128   */
+#define ME_WGRAD_FORM_TILE_128_64 10  /* <cout tile, cin tile>: MILLIEYE_WGRAD_TILE=128 with one channel count below 128    */
+#define ME_WGRAD_FORM_TILE_64_128 11
+#define ME_WGRAD_FORM_MFMA_VEC 12     /* conv_wgrad_mfma_kernel<true>: 16-byte loads                                        */
+#define ME_WGRAD_FORM_MFMA_SCALAR 13  /* conv_wgrad_mfma_kernel<false>: channels or pitches % 4 != 0, or unaligned pointers */
+#define ME_WGRAD_REDUCE_NONE 0        /* one slice, OHWI or 1x1: written straight to dw                                     */
+#define ME_WGRAD_REDUCE_FLAT 1        /* conv_wgrad_reduce_kernel, element by element                                       */
+#define ME_WGRAD_REDUCE_FLAT_V4 2     /* conv_wgrad_reduce_v4_kernel: count % 4 == 0, dw and workspace 16-byte aligned      */
+#define ME_WGRAD_REDUCE_OIHW 3        /* conv_wgrad_reduce_oihw_kernel reading the slabs element by element                 */
+#define ME_WGRAD_REDUCE_OIHW_V4 4     /* the same with 16-byte reads: cin % 4 == 0, workspace 16-byte aligned               */
+#define ME_WGRAD_REDUCE_STEM 5        /* stem_wgrad_reduce_kernel (either layout)                                           */
+#define ME_WGRAD_REDUCE_OIHW_FLAT 6   /* conv_wgrad_reduce_kernel transposing: OIHW with cout >= 65536                      */
+int me_conv_wgrad_form(const float* x, int64_t x_pitch, const float* dy, int64_t dy_pitch, const float* dw, int32_t n, int32_t h,
+                       int32_t w, int32_t cin, int32_t cout, int32_t ksize, int32_t stride, int32_t pad, const void* workspace,
+                       int64_t workspace_bytes, int32_t oihw, int32_t* splits, int32_t* reduce);
 /* me_pack_conv_f32 - one launch from a conv block's parameters (nn.Conv2d weight [cout][cin][k][k] + bias, optional
  * nn.BatchNorm2d gamma / beta / running mean / running var, reference yolov3/models.py:22-41) to every packed copy the fp32
  * kernels read: ohwi [cout][k][k][cin] (me_conv_desc.wgt), tiled [k*k][cin/16][cout][16] (wgt_tiled; NULL or cin % 16 == 0),

@@ -1974,6 +1974,7 @@ int me_conv_wgrad_f32(const float* x, int64_t x_pitch, const float* dy, int64_t 
   ME_REQUIRE(x && dy && dw, ME_E_NULLPTR, "me_conv_wgrad_f32: null pointer");
   ME_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && ksize >= 1 && ksize <= 7 && stride >= 1 && pad >= 0,
              ME_E_BADARG, "me_conv_wgrad_f32: bad dimensions");
+  ME_REQUIRE(h + 2 * pad >= ksize && w + 2 * pad >= ksize, ME_E_BADARG, "me_conv_wgrad_f32: the filter is larger than the padded map");
   const int ho = (h + 2 * pad - ksize) / stride + 1, wo = (w + 2 * pad - ksize) / stride + 1;
   dim3 grid((cin + 63) / 64, (cout + 63) / 64, ksize * ksize);
   hipLaunchKernelGGL(conv_wgrad_kernel, grid, dim3(256), 0, stream, x, (long long)x_pitch, dy, (long long)dy_pitch, dw,
@@ -2058,12 +2059,15 @@ extern "C++" {
 namespace me_wg9 {  // wgrad9.hip: all nine taps of a (cout, cin) tile per workgroup (3x3, stride 1, pad 1)
 bool shape(int cin, int cout, int ksize, int stride, int pad, int* tco, int* tci);
 int splits(int n, int h, int w, int cin, int cout, int* per);
+int wave_groups();
+bool eligible(const float* x, long long xp, const float* dy, long long dyp, int n, int h, int w, int cin, int cout);
 int launch(const float* x, long long xp, const float* dy, long long dyp, float* slabs, int n, int h, int w, int cin, int cout,
            hipStream_t stream, int* splits_out);
 }  // namespace me_wg9
 }  // extern "C++"
 
 int64_t me_conv_wgrad_workspace_bytes(int32_t n, int32_t ho, int32_t wo, int32_t cin, int32_t cout, int32_t ksize) {
+  if (n <= 0 || ho <= 0 || wo <= 0 || cin <= 0 || cout <= 0 || ksize < 1) return 0;  // (the call itself refuses these; no tiles to divide by)
   if (stem_wgrad_shape(cin, cout, ksize)) return (int64_t)SW_BLOCKS * cout * 27 * (int64_t)sizeof(float);
   int s = wgrad_splits((long long)n * ho * wo, cin, cout, ksize);
   const int s16 = wgrad_splits_h16((long long)n * ho * wo, cin, cout, ksize);   // (the 16-bit form slices by its own tiles)
@@ -2077,19 +2081,137 @@ int64_t me_conv_wgrad_workspace_bytes(int32_t n, int32_t ho, int32_t wo, int32_t
   return need;
 }
 
-static int wgrad_mfma(const float* x, int64_t x_pitch, const float* dy, int64_t dy_pitch, float* dw, int32_t n, int32_t h,
-                      int32_t w, int32_t cin, int32_t cout, int32_t ksize, int32_t stride, int32_t pad, void* workspace,
-                      int64_t workspace_bytes, void* stream_, int oihw) {
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+static int wgrad_depth() {   // stages of loads in flight per lane (round 5; 0 / 1 = the round-3 kernels, A/B)
+  static const int depth = [] {
+    const char* e = getenv("MILLIEYE_WGRAD_DEPTH");
+    return e ? atoi(e) : 4;
+  }();
+  return depth;
+}
+
+// What one call of me_conv_wgrad_mfma_f32 / _oihw_f32 runs.  wgrad_plan is the ONLY statement of the rules: the launcher below
+// launches what it says, me_conv_wgrad_form reports it.  No HIP call in here.
+struct WgradPlan {
+  int form;      // ME_WGRAD_FORM_*
+  int reduce;    // ME_WGRAD_REDUCE_*
+  int splits;    // slabs summed by the reduction (the stem: its SW_BLOCKS partials); 1 with ME_WGRAD_REDUCE_NONE = direct write
+  int per;       // pixels per slice of the per-tap kernels (a multiple of 16)
+  int tco, tci;  // tile of the per-tap kernels
+  int ho, wo;
+  long long count;
+};
+
+static int wgrad_plan(const float* x, int64_t x_pitch, const float* dy, int64_t dy_pitch, const float* dw, int32_t n, int32_t h,
+                      int32_t w, int32_t cin, int32_t cout, int32_t ksize, int32_t stride, int32_t pad, const void* workspace,
+                      int64_t workspace_bytes, int oihw, WgradPlan& pl) {
   ME_REQUIRE(x && dy && dw, ME_E_NULLPTR, "me_conv_wgrad_mfma_f32: null pointer");
   ME_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && ksize >= 1 && ksize <= 7 && stride >= 1 && pad >= 0,
              ME_E_BADARG, "me_conv_wgrad_mfma_f32: bad dimensions");
+  ME_REQUIRE(h + 2 * pad >= ksize && w + 2 * pad >= ksize, ME_E_BADARG, "me_conv_wgrad_mfma_f32: the filter is larger than the padded map");
   const int ho = (h + 2 * pad - ksize) / stride + 1, wo = (w + 2 * pad - ksize) / stride + 1;
   const long long P = (long long)n * ho * wo;
   ME_REQUIRE(P < (1ll << 31), ME_E_TOOBIG, "me_conv_wgrad_mfma_f32: too many output pixels");
   const long long count = (long long)cout * ksize * ksize * cin;
+  pl.ho = ho;
+  pl.wo = wo;
+  pl.count = count;
+  pl.per = 0;
+  pl.tco = pl.tci = 64;
   if (stem_wgrad_shape(cin, cout, ksize) && dy_pitch % 4 == 0 && me::aligned16(dy) && workspace &&
       workspace_bytes >= (int64_t)SW_BLOCKS * count * (int64_t)sizeof(float) && (cout + 31) / 32 < 65536) {
+    pl.form = ME_WGRAD_FORM_STEM;
+    pl.reduce = ME_WGRAD_REDUCE_STEM;
+    pl.splits = SW_BLOCKS;
+    return pl.form;
+  }
+  int splits = wgrad_splits(P, cin, cout, ksize);
+  bool nine = false;
+  {
+    int tco9, tci9;
+    if (me_wg9::shape(cin, cout, ksize, stride, pad, &tco9, &tci9) && h == ho && w == wo && workspace) {
+      const int s9 = me_wg9::splits(n, h, w, cin, cout, nullptr);
+      if (workspace_bytes >= (int64_t)s9 * count * (int64_t)sizeof(float) &&
+          me_wg9::eligible(x, x_pitch, dy, dy_pitch, n, h, w, cin, cout)) {
+        splits = s9;
+        nine = true;
+      }
+    }
+  }
+  if (!nine && splits > 1 && (!workspace || workspace_bytes < (int64_t)splits * count * (int64_t)sizeof(float))) splits = 1;
+  ME_REQUIRE(!oihw || ksize == 1 || (workspace && workspace_bytes >= count * (int64_t)sizeof(float)), ME_E_BADARG,
+             "me_conv_wgrad_mfma_oihw_f32: needs a workspace of at least one slab (%lld bytes)", count * 4ll);
+  int per = (int)((P + splits - 1) / splits);
+  per = (per + 15) & ~15;
+  ME_REQUIRE((long long)ksize * ksize * splits < 65536, ME_E_TOOBIG, "me_conv_wgrad_mfma_f32: grid too large");
+  const bool via_ws = nine || splits > 1 || (oihw && ksize > 1);  // (a 1x1 filter's OHWI and OIHW layouts coincide)
+  pl.splits = splits;
+  pl.per = per;
+  if (!via_ws)
+    pl.reduce = ME_WGRAD_REDUCE_NONE;
+  else if (oihw && ksize > 1 && cout < 65536)
+    pl.reduce = ((cin & 3) == 0 && me::aligned16(workspace)) ? ME_WGRAD_REDUCE_OIHW_V4 : ME_WGRAD_REDUCE_OIHW;
+  else if (!(oihw && ksize > 1) && count % 4 == 0 && me::aligned16(dw) && me::aligned16(workspace))
+    pl.reduce = ME_WGRAD_REDUCE_FLAT_V4;
+  else
+    pl.reduce = (oihw && ksize > 1) ? ME_WGRAD_REDUCE_OIHW_FLAT : ME_WGRAD_REDUCE_FLAT;
+  if (nine) {
+    pl.form = me_wg9::wave_groups() == 2 ? ME_WGRAD_FORM_NINE_TAP : ME_WGRAD_FORM_NINE_TAP_4W;
+    return pl.form;
+  }
+  const bool vec = (cin % 4 == 0) && (cout % 4 == 0) && (x_pitch % 4 == 0) && (dy_pitch % 4 == 0) && me::aligned16(x) &&
+                   me::aligned16(dy);
+  int tco, tci;
+  wgrad_tile(P, cin, cout, ksize, tco, tci);
+  if (!vec) tco = tci = 64;  // (the split count was sized for the larger tile: correct, a few workgroups more)
+  pl.tco = tco;
+  pl.tci = tci;
+  const int depth = wgrad_depth();
+  if (vec && depth > 1 && cin <= 32 && tco == 64)
+    pl.form = ME_WGRAD_FORM_PIPE_64_32;   // half-wide tile, the wave pair of a co block splits the k-steps
+  else if (vec && depth > 4 && tco == 128 && tci == 128)   // (depth 5+: the four-deep pipeline on the full-width tiles, A/B only -
+    pl.form = ME_WGRAD_FORM_PIPE_128_128;                   //  measured neutral on the 1x1 filters, slower on 128 x 128)
+  else if (vec && depth > 4 && tco == 128)
+    pl.form = ME_WGRAD_FORM_PIPE_128_64;
+  else if (vec && depth > 4 && tci == 128)
+    pl.form = ME_WGRAD_FORM_PIPE_64_128;
+  else if (vec && depth > 4)
+    pl.form = ME_WGRAD_FORM_PIPE_64_64;
+  else if (vec && tco == 128 && tci == 128)
+    pl.form = ME_WGRAD_FORM_TILE_128_128;
+  else if (vec && tco == 128)
+    pl.form = ME_WGRAD_FORM_TILE_128_64;
+  else if (vec && tci == 128)
+    pl.form = ME_WGRAD_FORM_TILE_64_128;
+  else if (vec)
+    pl.form = ME_WGRAD_FORM_MFMA_VEC;
+  else
+    pl.form = ME_WGRAD_FORM_MFMA_SCALAR;
+  return pl.form;
+}
+
+int me_conv_wgrad_form(const float* x, int64_t x_pitch, const float* dy, int64_t dy_pitch, const float* dw, int32_t n, int32_t h,
+                       int32_t w, int32_t cin, int32_t cout, int32_t ksize, int32_t stride, int32_t pad, const void* workspace,
+                       int64_t workspace_bytes, int32_t oihw, int32_t* splits, int32_t* reduce) {
+  WgradPlan pl;
+  const int form = wgrad_plan(x, x_pitch, dy, dy_pitch, dw, n, h, w, cin, cout, ksize, stride, pad, workspace, workspace_bytes,
+                              oihw, pl);
+  if (form < 0) return form;
+  if (splits) *splits = pl.splits;
+  if (reduce) *reduce = pl.reduce;
+  return form;
+}
+
+static int wgrad_mfma(const float* x, int64_t x_pitch, const float* dy, int64_t dy_pitch, float* dw, int32_t n, int32_t h,
+                      int32_t w, int32_t cin, int32_t cout, int32_t ksize, int32_t stride, int32_t pad, void* workspace,
+                      int64_t workspace_bytes, void* stream_, int oihw) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  WgradPlan pl;
+  const int form = wgrad_plan(x, x_pitch, dy, dy_pitch, dw, n, h, w, cin, cout, ksize, stride, pad, workspace, workspace_bytes,
+                              oihw, pl);
+  if (form < 0) return form;
+  const int ho = pl.ho, wo = pl.wo, splits = pl.splits, per = pl.per;
+  const long long count = pl.count;
+  if (form == ME_WGRAD_FORM_STEM) {
     float* part = reinterpret_cast<float*>(workspace);
     hipLaunchKernelGGL(stem_wgrad_kernel, dim3(SW_BLOCKS, (cout + 31) / 32), dim3(256), 0, stream, x, (long long)x_pitch, dy,
                        (long long)dy_pitch, part, n, h, w, cout, stride, pad, ho, wo);
@@ -2097,98 +2219,72 @@ static int wgrad_mfma(const float* x, int64_t x_pitch, const float* dy, int64_t 
                        SW_BLOCKS, oihw);
     return me::check_launch("stem_wgrad_kernel");
   }
-  int splits = wgrad_splits(P, cin, cout, ksize);
-  bool done9 = false;
-  {
-    int tco9, tci9;
-    if (me_wg9::shape(cin, cout, ksize, stride, pad, &tco9, &tci9) && h == ho && w == wo && workspace) {
-      const int s9 = me_wg9::splits(n, h, w, cin, cout, nullptr);
-      if (workspace_bytes >= (int64_t)s9 * count * (int64_t)sizeof(float)) {
-        int sp = 0;
-        const int rc9 = me_wg9::launch(x, x_pitch, dy, dy_pitch, reinterpret_cast<float*>(workspace), n, h, w, cin, cout, stream, &sp);
-        if (rc9 > 0) return rc9;
-        if (rc9 == 0) {
-          splits = sp;
-          done9 = true;
-        }
-      }
-    }
-  }
-  if (splits > 1 && (!workspace || workspace_bytes < (int64_t)splits * count * (int64_t)sizeof(float))) splits = 1;
-  ME_REQUIRE(!oihw || ksize == 1 || (workspace && workspace_bytes >= count * (int64_t)sizeof(float)), ME_E_BADARG,
-             "me_conv_wgrad_mfma_oihw_f32: needs a workspace of at least one slab (%lld bytes)", count * 4ll);
-  int per = (int)((P + splits - 1) / splits);
-  per = (per + 15) & ~15;
-  ME_REQUIRE((long long)ksize * ksize * splits < 65536, ME_E_TOOBIG, "me_conv_wgrad_mfma_f32: grid too large");
-  const bool via_ws = done9 || splits > 1 || (oihw && ksize > 1);  // (a 1x1 filter's OHWI and OIHW layouts coincide)
+  const bool via_ws = pl.reduce != ME_WGRAD_REDUCE_NONE;
   float* out = via_ws ? reinterpret_cast<float*>(workspace) : dw;
-  const bool vec = (cin % 4 == 0) && (cout % 4 == 0) && (x_pitch % 4 == 0) && (dy_pitch % 4 == 0) && me::aligned16(x) &&
-                   me::aligned16(dy);
-  int tco, tci;
-  wgrad_tile(P, cin, cout, ksize, tco, tci);
-  if (!vec) tco = tci = 64;  // (the split count was sized for the larger tile: correct, a few workgroups more)
-  dim3 grid((cin + tci - 1) / tci, (cout + tco - 1) / tco, ksize * ksize * splits);
-  static const int depth = [] {   // stages of loads in flight per lane (round 5; 0 / 1 = the round-3 kernels, A/B)
-    const char* e = getenv("MILLIEYE_WGRAD_DEPTH");
-    return e ? atoi(e) : 4;
-  }();
-  if (done9) {
+  dim3 grid((cin + pl.tci - 1) / pl.tci, (cout + pl.tco - 1) / pl.tco, ksize * ksize * splits);
+  if (form == ME_WGRAD_FORM_NINE_TAP || form == ME_WGRAD_FORM_NINE_TAP_4W) {
     // (slabs written by the nine-tap kernel: straight to the reduction)
-  } else
+    int sp = 0;
+    const int rc9 = me_wg9::launch(x, x_pitch, dy, dy_pitch, reinterpret_cast<float*>(workspace), n, h, w, cin, cout, stream, &sp);
+    if (rc9 > 0) return rc9;
+    ME_REQUIRE(rc9 == 0 && sp == splits, ME_E_BADARG, "me_conv_wgrad_mfma_f32: the nine-tap launcher disagrees with the plan");
+  } else {
 #define ME_WG_TILE(A, B)                                                                                              \
   hipLaunchKernelGGL((conv_wgrad_tile_kernel<A, B>), grid, dim3(256), 0, stream, x, (long long)x_pitch, dy,           \
                      (long long)dy_pitch, out, n, h, w, cin, cout, ksize, stride, pad, ho, wo, splits, per)
 #define ME_WG_PIPE(A, B, D)                                                                                           \
   hipLaunchKernelGGL((conv_wgrad_pipe_kernel<A, B, D>), grid, dim3(256), 0, stream, x, (long long)x_pitch, dy,        \
                      (long long)dy_pitch, out, n, h, w, cin, cout, ksize, stride, pad, ho, wo, splits, per)
-  if (vec && depth > 1 && cin <= 32 && tco == 64) {
-    grid.x = 1;
-    ME_WG_PIPE(64, 32, 4);   // half-wide tile, the wave pair of a co block splits the k-steps
-  } else if (vec && depth > 4 && tco == 128 && tci == 128)   // (depth 5+: the four-deep pipeline on the full-width tiles, A/B only -
-    ME_WG_PIPE(128, 128, 4);                                  //  measured neutral on the 1x1 filters, slower on 128 x 128)
-  else if (vec && depth > 4 && tco == 128)
-    ME_WG_PIPE(128, 64, 4);
-  else if (vec && depth > 4 && tci == 128)
-    ME_WG_PIPE(64, 128, 4);
-  else if (vec && depth > 4)
-    ME_WG_PIPE(64, 64, 4);
-  else if (vec && tco == 128 && tci == 128)
-    ME_WG_TILE(128, 128);
-  else if (vec && tco == 128)
-    ME_WG_TILE(128, 64);
-  else if (vec && tci == 128)
-    ME_WG_TILE(64, 128);
-  else if (vec) {
-    static const int abl = [] {
-      const char* on = getenv("MILLIEYE_ABLATION");
-      const char* e = getenv("MILLIEYE_WGRAD_ABL");
-      return (on && on[0] == '1' && e) ? atoi(e) : 0;
-    }();
 #define ME_WG_ABL(A)                                                                                                   \
   hipLaunchKernelGGL((conv_wgrad_mfma_kernel<true, A>), grid, dim3(256), 0, stream, x, (long long)x_pitch, dy,          \
                      (long long)dy_pitch, out, n, h, w, cin, cout, ksize, stride, pad, ho, wo, splits, per)
-    if (abl == 1) ME_WG_ABL(1);
-    else if (abl == 2) ME_WG_ABL(2);
-    else ME_WG_ABL(0);
+    switch (form) {
+      case ME_WGRAD_FORM_PIPE_64_32:
+        grid.x = 1;
+        ME_WG_PIPE(64, 32, 4);
+        break;
+      case ME_WGRAD_FORM_PIPE_128_128: ME_WG_PIPE(128, 128, 4); break;
+      case ME_WGRAD_FORM_PIPE_128_64: ME_WG_PIPE(128, 64, 4); break;
+      case ME_WGRAD_FORM_PIPE_64_128: ME_WG_PIPE(64, 128, 4); break;
+      case ME_WGRAD_FORM_PIPE_64_64: ME_WG_PIPE(64, 64, 4); break;
+      case ME_WGRAD_FORM_TILE_128_128: ME_WG_TILE(128, 128); break;
+      case ME_WGRAD_FORM_TILE_128_64: ME_WG_TILE(128, 64); break;
+      case ME_WGRAD_FORM_TILE_64_128: ME_WG_TILE(64, 128); break;
+      case ME_WGRAD_FORM_MFMA_VEC: {
+        static const int abl = [] {
+          const char* on = getenv("MILLIEYE_ABLATION");
+          const char* e = getenv("MILLIEYE_WGRAD_ABL");
+          return (on && on[0] == '1' && e) ? atoi(e) : 0;
+        }();
+        if (abl == 1) ME_WG_ABL(1);
+        else if (abl == 2) ME_WG_ABL(2);
+        else ME_WG_ABL(0);
+        break;
+      }
+      default:   // ME_WGRAD_FORM_MFMA_SCALAR
+        hipLaunchKernelGGL(conv_wgrad_mfma_kernel<false>, grid, dim3(256), 0, stream, x, (long long)x_pitch, dy,
+                           (long long)dy_pitch, out, n, h, w, cin, cout, ksize, stride, pad, ho, wo, splits, per);
+    }
 #undef ME_WG_ABL
-  }
 #undef ME_WG_TILE
 #undef ME_WG_PIPE
-  else
-    hipLaunchKernelGGL(conv_wgrad_mfma_kernel<false>, grid, dim3(256), 0, stream, x, (long long)x_pitch, dy,
-                       (long long)dy_pitch, out, n, h, w, cin, cout, ksize, stride, pad, ho, wo, splits, per);
+  }
   int rc = me::check_launch("conv_wgrad_mfma_kernel");
   if (rc || !via_ws) return rc;
   const float* slabs = reinterpret_cast<const float*>(workspace);
-  if (oihw && ksize > 1 && cout < 65536) {
-    const int kk = ksize * ksize;
-    hipLaunchKernelGGL(conv_wgrad_reduce_oihw_kernel, dim3((cin + 63) / 64, cout), dim3(256), 64 * (kk | 1) * sizeof(float),
-                       stream, slabs, dw, count, splits, kk, cin, ((cin & 3) == 0 && me::aligned16(workspace)) ? 1 : 0);
-  } else if (!(oihw && ksize > 1) && count % 4 == 0 && me::aligned16(dw) && me::aligned16(workspace)) {
-    hipLaunchKernelGGL(conv_wgrad_reduce_v4_kernel, dim3(grid1d(count / 4)), dim3(256), 0, stream, slabs, dw, count / 4, splits);
-  } else {
-    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3(grid1d(count)), dim3(256), 0, stream, slabs, dw, count, splits,
-                       (oihw && ksize > 1) ? ksize * ksize : 0, cin);
+  const int kk = ksize * ksize;
+  switch (pl.reduce) {
+    case ME_WGRAD_REDUCE_OIHW:
+    case ME_WGRAD_REDUCE_OIHW_V4:
+      hipLaunchKernelGGL(conv_wgrad_reduce_oihw_kernel, dim3((cin + 63) / 64, cout), dim3(256), 64 * (kk | 1) * sizeof(float),
+                         stream, slabs, dw, count, splits, kk, cin, pl.reduce == ME_WGRAD_REDUCE_OIHW_V4 ? 1 : 0);
+      break;
+    case ME_WGRAD_REDUCE_FLAT_V4:
+      hipLaunchKernelGGL(conv_wgrad_reduce_v4_kernel, dim3(grid1d(count / 4)), dim3(256), 0, stream, slabs, dw, count / 4, splits);
+      break;
+    default:   // ME_WGRAD_REDUCE_FLAT, ME_WGRAD_REDUCE_OIHW_FLAT
+      hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3(grid1d(count)), dim3(256), 0, stream, slabs, dw, count, splits,
+                         pl.reduce == ME_WGRAD_REDUCE_OIHW_FLAT ? kk : 0, cin);
   }
   return me::check_launch("conv_wgrad_reduce_kernel");
 }
@@ -2215,6 +2311,7 @@ int me_conv_wgrad_h16(const void* x_, int64_t x_pitch, const void* dy_, int64_t 
   ME_REQUIRE(x && dy && dw, ME_E_NULLPTR, "me_conv_wgrad_h16: null pointer");
   ME_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && ksize >= 1 && ksize <= 7 && stride >= 1 && pad >= 0,
              ME_E_BADARG, "me_conv_wgrad_h16: bad dimensions");
+  ME_REQUIRE(h + 2 * pad >= ksize && w + 2 * pad >= ksize, ME_E_BADARG, "me_conv_wgrad_h16: the filter is larger than the padded map");
   ME_REQUIRE(half_type == 0 || half_type == 1, ME_E_BADARG, "me_conv_wgrad_h16: half_type must be 0 (bf16) or 1 (f16)");
   ME_REQUIRE(cin % 8 == 0 && cout % 8 == 0 && x_pitch % 8 == 0 && dy_pitch % 8 == 0 && me::aligned16(x) && me::aligned16(dy),
              ME_E_ALIGN, "me_conv_wgrad_h16: channels and pitches must be multiples of 8 and the tensors 16-byte aligned");

@@ -293,32 +293,57 @@ int splits(int n, int h, int w, int cin, int cout, int* per) {
   return (int)s;
 }
 
+// wave groups per workgroup: 2 = eight waves merging through LDS (default), 1 = four waves
+int wave_groups() {
+  static const int NG = [] {
+    const char* e = getenv("MILLIEYE_WGRAD9_NG");
+    return (e && e[0] == '1') ? 1 : 2;
+  }();
+  return NG;
+}
+
+// dynamic LDS of one workgroup on a map of width w
+static size_t lds_bytes(int w, int tco, int tci, int* hb_out, int* nr_out) {
+  const int NG = wave_groups();
+  const int hb = (w + 1 + 1 + 15) / 16, nr = 2 * hb + 2 * NG;
+  size_t lds = ((size_t)2 * 16 * NG * tco + (size_t)(nr + 1) * 16 * tci) * sizeof(float);
+  const size_t xch = (size_t)4 * 144 * 64 * sizeof(float);   // accumulator exchange of the second half
+  if (NG == 2 && lds < xch) lds = xch;
+  if (hb_out) *hb_out = hb;
+  if (nr_out) *nr_out = nr;
+  return lds;
+}
+
+// everything `launch` needs beyond `shape`: operands 16-byte aligned, the padded positions in 31 bits, the ring of a map this
+// wide inside the LDS, the halo shorter than one image.  False: the layer stays on the per-tap kernels.
+bool eligible(const float* x, long long xp, const float* dy, long long dyp, int n, int h, int w, int cin, int cout) {
+  int tco, tci;
+  if (!shape(cin, cout, 3, 1, 1, &tco, &tci)) return false;
+  if (xp % 4 || dyp % 4 || !me::aligned16(x) || !me::aligned16(dy)) return false;
+  const int Wp = w + 1;
+  const long long Ip = (long long)(h + 1) * Wp;
+  if (Ip >= (1ll << 31) || (long long)n * Ip >= (1ll << 31)) return false;
+  int hb;
+  if (lds_bytes(w, tco, tci, &hb, nullptr) > 160 * 1024) return false;
+  if (Ip <= 16 * hb) return false;  // (pos_of assumes the halo is shorter than one image)
+  return true;
+}
+
 // slabs [split][cout][9][cin] of partial sums into `slabs`; the caller reduces them.  Returns < 0 when the layer is not
-// eligible after all (map too wide for the LDS ring, operands not 16-byte aligned): the caller falls back to the per-tap kernel.
+// `eligible` (the caller asks first and stays on the per-tap kernels).
 int launch(const float* x, long long xp, const float* dy, long long dyp, float* slabs, int n, int h, int w, int cin, int cout,
            hipStream_t stream, int* splits_out) {
   int tco, tci;
-  if (!shape(cin, cout, 3, 1, 1, &tco, &tci)) return -1;
-  if (xp % 4 || dyp % 4 || !me::aligned16(x) || !me::aligned16(dy)) return -1;
+  if (!eligible(x, xp, dy, dyp, n, h, w, cin, cout) || !shape(cin, cout, 3, 1, 1, &tco, &tci)) return -1;
   W9Args a = {};
   a.x = x; a.xp = xp; a.dy = dy; a.dyp = dyp; a.out = slabs;
   a.n = n; a.h = h; a.w = w; a.cin = cin; a.cout = cout;
   a.Wp = w + 1;
   a.Ip = (h + 1) * a.Wp;
   a.Mp = (long long)n * a.Ip;
-  if (a.Mp >= (1ll << 31)) return -1;
-  static const int NG = [] {   // wave groups per workgroup: 2 = eight waves merging through LDS (default), 1 = four waves
-    const char* e = getenv("MILLIEYE_WGRAD9_NG");
-    return (e && e[0] == '1') ? 1 : 2;
-  }();
-  a.hb = (a.Wp + 1 + 15) / 16;
-  a.nr = 2 * a.hb + 2 * NG;
-  size_t lds = ((size_t)2 * 16 * NG * tco + (size_t)(a.nr + 1) * 16 * tci) * sizeof(float);
-  const size_t xch = (size_t)4 * 144 * 64 * sizeof(float);   // accumulator exchange of the second half
-  if (NG == 2 && lds < xch) lds = xch;
-  if (lds > 160 * 1024) return -1;
+  const int NG = wave_groups();
+  const size_t lds = lds_bytes(w, tco, tci, &a.hb, &a.nr);
   const int s = splits(n, h, w, cin, cout, &a.per);
-  if (a.Ip <= 16 * a.hb) return -1;  // (pos_of assumes the halo is shorter than one image)
   static bool attr_set = false;
   if (!attr_set) {
     ME_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad9_kernel<2, 2, 1>),

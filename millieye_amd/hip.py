@@ -191,6 +191,13 @@ RADAR_STATUS = {1: ("points that pass the filter", RADAR_MAX_POINTS), 2: ("clust
 
 ADAM_MAX_TENSORS = 64
 
+# me_conv_wgrad_form (include/millieye_hip.h): ME_WGRAD_FORM_* / ME_WGRAD_REDUCE_* by name
+WGRAD_FORMS = {"stem": 1, "nine_tap": 2, "nine_tap_4w": 3, "pipe_64_32": 4, "pipe_128_128": 5, "pipe_128_64": 6, "pipe_64_128": 7,
+               "pipe_64_64": 8, "tile_128_128": 9, "tile_128_64": 10, "tile_64_128": 11, "mfma_vec": 12, "mfma_scalar": 13}
+WGRAD_REDUCES = {"none": 0, "flat": 1, "flat_v4": 2, "oihw": 3, "oihw_v4": 4, "stem": 5, "oihw_flat": 6}
+WGRAD_FORM_NAMES = {v: k for k, v in WGRAD_FORMS.items()}
+WGRAD_REDUCE_NAMES = {v: k for k, v in WGRAD_REDUCES.items()}
+
 
 class AdamDesc(C.Structure):
     """me_adam_desc: one optimizer step over up to 64 fp32 tensors (csrc/optim.hip)."""
@@ -356,6 +363,8 @@ SIGNATURES = {
     "me_nms_batched_prepped_f32": (C.c_int, [C.c_void_p, C.c_void_p]),
     "me_conv_wgrad_mfma_oihw_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int32] * 8
                                     + [C.c_void_p, C.c_int64, C.c_void_p]),
+    "me_conv_wgrad_form": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int32] * 8
+                           + [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "me_pack_conv_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_float]
                          + [C.c_void_p] * 7),
     "me_roi_align_bwd_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -1144,6 +1153,18 @@ def conv_wgrad(x_nhwc, dy_nhwc, ksize, stride, pad, oihw=False):
     check(fn(x_nhwc.data_ptr(), x_nhwc.stride(2), dy_nhwc.data_ptr(), dy_nhwc.stride(2), dw.data_ptr(), n, h, w, cin, cout,
              ksize, stride, pad, ws_ptr, need, stream_ptr()), "me_conv_wgrad_mfma_f32")
     return dw
+
+
+def wgrad_form(x_ptr, x_pitch, dy_ptr, dy_pitch, dw_ptr, n, h, w, cin, cout, ksize, stride, pad, ws_ptr, ws_bytes, oihw=False):
+    """What ``me_conv_wgrad_mfma_f32`` / ``_oihw_f32`` would run on these arguments (``me_conv_wgrad_form``: the launcher's own
+    decision, no GPU needed; the addresses are only tested for NULL and alignment): (form name, slice count, reduction name), or
+    (negative ME_E_* code, None, None) where the call would refuse."""
+    splits, reduce_ = C.c_int32(-1), C.c_int32(-1)
+    rc = lib().me_conv_wgrad_form(x_ptr, x_pitch, dy_ptr, dy_pitch, dw_ptr, n, h, w, cin, cout, ksize, stride, pad, ws_ptr,
+                                  ws_bytes, 1 if oihw else 0, C.byref(splits), C.byref(reduce_))
+    if rc < 0:
+        return rc, None, None
+    return WGRAD_FORM_NAMES[rc], splits.value, WGRAD_REDUCE_NAMES[reduce_.value]
 
 
 def frame_means(imgs):
