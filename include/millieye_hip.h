@@ -765,7 +765,8 @@ int me_image_batch_pad_resize_flip_u8_f32(const uint8_t* src, int64_t src_bytes,
  * and each of R, G, B then goes through the (float)c / 255.f of the RGB path: a frame in format F gives the bits
  * me_image_batch_pad_resize_flip_u8_f32 gives on that frame converted to RGB.  A frame whose bytes do not lie inside src,
  * whose format id is unknown, or whose h / w is odd where its format needs it even (NV12: both, YUYV: w) is not read and
- * comes out all zero.  No row pitch: frames are dense. */
+ * comes out all zero.  No row pitch: frames are dense (pitched, cropped and device-resident frames:
+ * me_image_batch_surfaces_u8_f32). */
 #define ME_PIXFMT_RGB 0
 #define ME_PIXFMT_BGR 1
 #define ME_PIXFMT_NV12 2
@@ -832,6 +833,41 @@ int me_radar_heatmap_rect_f32(const double* points, const int32_t* offsets, cons
                               int32_t radar_maps_size, float* out, int32_t map_h, int32_t map_w, void* stream);
 int me_radar_boxes_letterbox_f32(const double* proposals, const int32_t* counts, const int32_t* frame_size, int32_t streams,
                                  int32_t height, int32_t width, float* boxes, int32_t* box_counts, void* stream);
+/* me_image_batch_surfaces_u8_f32: the ragged batch read where the frames LIE - with a row pitch, from a buffer per frame, from a
+ * region of a larger picture - instead of from one dense packed buffer: a V4L2 buffer has bytesperline >= width * bpp, a
+ * hardware decoder gives NV12 with an aligned pitch and the UV plane behind an aligned height, and its surface already lies in
+ * device memory.  No src: desc [n,10] int64 on the device, one row per frame:
+ *   0 base      device address of the first byte of the buffer the picture lives in (frames may name different buffers)
+ *   1 bytes     length of that buffer; nothing outside [base, base + bytes) is ever read
+ *   2 off       byte offset of the picture's first byte (the packed plane, or the Y plane)
+ *   3 h, 4 w    the picture's size in pixels
+ *   5 flip      as in the [n,5] descriptor
+ *   6 fmt       ME_PIXFMT_*
+ *   7 pitch     bytes between consecutive rows of plane 0
+ *   8 uv_off    NV12 only: byte offset of the interleaved UV plane from base (ignored otherwise)
+ *   9 uv_pitch  NV12 only: bytes between UV rows (ignored otherwise)
+ * Fetches, in 64-bit addresses (off + sy * pitch may lie beyond 2^31): RGB / BGR pixel (sy,sx) = base + off + sy * pitch + 3 sx;
+ * YUYV row sy = base + off + sy * pitch; NV12 Y = base[off + sy * pitch + sx], U, V at base + uv_off + (sy >> 1) * uv_pitch +
+ * (sx & ~1).  dst [n,3,height,width] float32, one launch.
+ *   resize == 0: the nearest resize under the letterbox rule of me_image_batch_letterbox_u8_f32 (height == width: pad_to_square).
+ *   resize == 1: the area-averaging resize of me_image_batch_area_u8_f32; needs height == width (ME_E_BADARG otherwise: there
+ *                is no rectangular area form).  Any other value: ME_E_BADARG.
+ * Frame f of dst is bit-identical to what that dense entry point gives on the frame's pixels copied into a dense frame with the
+ * same h, w, flip, fmt: the integer YUV conversion, (float)c / 255.f, the window rule and the single division of the area
+ * resize, the index arithmetic and the float4 stores for width % 4 == 0 (dst 16-byte aligned, ME_E_ALIGN otherwise) are the
+ * same code.  Pitch padding, bytes between the planes and bytes of the buffer outside the picture never influence the output
+ * (the area kernel's 16-byte loads may read them, inside the buffer; they reach no sum).
+ * Validity per frame, every test in 64 bits and by division (no product of descriptor values can overflow), with row = 3w
+ * (RGB / BGR), 2w (YUYV) or w (NV12 Y) bytes:
+ *   base != 0, bytes > 0;  1 <= h, w <= 2^30;  fmt known and its parity rule kept (NV12: h, w even; YUYV: w even);
+ *   pitch >= row (negative and bottom-up pitches are invalid);  0 <= off <= bytes - row;  h - 1 <= (bytes - row - off) / pitch;
+ *   NV12: uv_pitch >= w;  0 <= uv_off <= bytes - w;  h / 2 - 1 <= (bytes - w - uv_off) / uv_pitch;
+ *   resize == 0: the letterbox geometry is valid (Ph, Pw <= 2^30);  resize == 1: max(h, w) <= 255 * height.
+ * An invalid frame is not read and comes out all zero; its neighbours in the batch are unaffected.
+ * Arguments as for the letterbox entry point: n <= 65535, height * width < 2^30, null pointers refused, n == 0 is a no-op.
+ * The buffers must stay alive until the launch has run. */
+int me_image_batch_surfaces_u8_f32(const int64_t* desc, int32_t n, float* dst, int32_t height, int32_t width, int32_t resize,
+                                   void* stream);
 
 /* ---- multi-stream front of the live demos (csrc/radar.hip) ----------------------------------
  * me_radar_proposals_f64: the per-frame radar proposal chain of module3_our_dataset/run_mp.py:65-135 (= run_sp.py:117-175)

@@ -13,6 +13,9 @@
 //   me_image_batch_letterbox_u8_f32
 //                               the same ragged batch letterboxed to a rectangular H x W canvas (letterbox.h), for the
 //                               rectangular network input; torch's F.pad + F.interpolate(nearest) bit for bit.
+//   me_image_batch_surfaces_u8_f32
+//                               the letterbox and the area kernel reading every frame through a descriptor of its own
+//                               (buffer, offset, row pitch, NV12 chroma plane): pitched, cropped and device-resident frames.
 //   me_radar_heatmap_rect_f32   me_radar_heatmap_f32 with a rectangular mh x mw output (the bins letterboxed the same way).
 //   me_radar_heatmap_f32        plot_radar_heatmap (:59-106: three np.histogram2d in float64, per-bin means, range
 //                               normalisation) + ToTensor().float() (:267) + pad_to_square (:270) +
@@ -176,6 +179,65 @@ __device__ inline void fetch_rgb_u8(const unsigned char* __restrict__ frame, int
   }
 }
 
+// ---- surfaces: frames read where they lie ------------------------------------------------------------------------------
+// One row of the [n,10] descriptor of me_image_batch_surfaces_u8_f32 = (base, bytes, off, h, w, flip, fmt, pitch, uv_off,
+// uv_pitch): a picture inside a buffer [base, base + bytes) of its own, rows `pitch` bytes apart, the NV12 chroma plane at an
+// offset and with a pitch of its own.  The letterbox and the area kernel below are instantiated for it (kSurf); only the
+// addresses differ from the dense frames, so a surface gives the bits of its pixels copied into a dense frame.
+struct Surface {
+  const unsigned char* base;
+  long long bytes, off, h, w, fmt, pitch, uv_off, uv_pitch;
+  int flip;
+  bool valid;
+};
+
+// The validity rule of a [n,10] row, in 64 bits and with divisions like format_frame_valid: the rows of plane 0 (and of the
+// NV12 chroma plane) lie inside [0, bytes).  An invalid surface is never read.
+__device__ inline Surface load_surface(const long long* __restrict__ d) {
+  Surface s;
+  s.base = reinterpret_cast<const unsigned char*>(d[0]);
+  s.bytes = d[1], s.off = d[2], s.h = d[3], s.w = d[4], s.flip = d[5] != 0, s.fmt = d[6];
+  s.pitch = d[7], s.uv_off = d[8], s.uv_pitch = d[9];
+  bool valid = d[0] != 0 && s.bytes > 0 && s.h >= 1 && s.w >= 1 && s.h <= (1ll << 30) && s.w <= (1ll << 30);
+  long long row = 1;   // bytes of one row of plane 0
+  if (s.fmt == ME_PIXFMT_RGB || s.fmt == ME_PIXFMT_BGR)
+    row = 3 * s.w;
+  else if (s.fmt == ME_PIXFMT_NV12)
+    row = s.w, valid = valid && (s.h & 1) == 0 && (s.w & 1) == 0;
+  else if (s.fmt == ME_PIXFMT_YUYV)
+    row = 2 * s.w, valid = valid && (s.w & 1) == 0;
+  else
+    valid = false;
+  valid = valid && s.pitch >= row && row <= s.bytes && s.off >= 0 && s.off <= s.bytes - row;
+  valid = valid && s.h - 1 <= (s.bytes - row - s.off) / s.pitch;
+  if (valid && s.fmt == ME_PIXFMT_NV12) {
+    valid = s.uv_pitch >= s.w && s.uv_off >= 0 && s.uv_off <= s.bytes - s.w;
+    valid = valid && s.h / 2 - 1 <= (s.bytes - s.w - s.uv_off) / s.uv_pitch;
+  }
+  // a pitch nobody steps by (a single row) may be any number: keep the address arithmetic small
+  if (s.h == 1) s.pitch = row;
+  if (s.h == 2) s.uv_pitch = s.w;
+  s.valid = valid;
+  return s;
+}
+
+// fetch_rgb_u8 for a valid surface: 64-bit byte addresses from base
+__device__ inline void fetch_rgb_u8(const Surface& s, int fmt, int sy, int sx, int& ri, int& gi, int& bi) {
+  const unsigned char* row = s.base + s.off + sy * s.pitch;
+  if (fmt == ME_PIXFMT_RGB || fmt == ME_PIXFMT_BGR) {
+    const unsigned char* p = row + 3 * sx;
+    ri = fmt == ME_PIXFMT_RGB ? p[0] : p[2];
+    gi = p[1];
+    bi = fmt == ME_PIXFMT_RGB ? p[2] : p[0];
+  } else if (fmt == ME_PIXFMT_NV12) {
+    const unsigned char* uv = s.base + s.uv_off + (sy >> 1) * s.uv_pitch + (sx & ~1);
+    yuv_to_rgb(row[sx], uv[0], uv[1], ri, gi, bi);
+  } else {
+    const int c = 4 * (sx >> 1);
+    yuv_to_rgb(row[2 * sx], row[c + 1], row[c + 3], ri, gi, bi);
+  }
+}
+
 __global__ __launch_bounds__(256) void image_batch_formats_kernel(const unsigned char* __restrict__ src,
                                                                   long long src_bytes,
                                                                   const long long* __restrict__ desc,
@@ -239,14 +301,19 @@ __global__ __launch_bounds__(256) void image_batch_formats_kernel(const unsigned
 // smallest (a k) x (b k) that holds the picture: k = max(ceil(h / a), ceil(w / b)) in 64 bits, Ph = a k, Pw = b k, so that
 // Ph / H == Pw / W exactly; floor(diff / 2) of the padding goes in front on each axis, the rest behind (letterbox.h).  Then
 // the nearest rule per axis.  H == W gives a = b = 1, Ph = Pw = max(h, w): the operations, and the bits, of image_batch_formats_kernel.
+// kSurf: desc is [n,10], one Surface per frame, and src / src_bytes are not used (me_image_batch_surfaces_u8_f32).
+template <bool kSurf>
 __global__ __launch_bounds__(256) void image_batch_letterbox_kernel(const unsigned char* __restrict__ src,
                                                                     long long src_bytes,
                                                                     const long long* __restrict__ desc,
                                                                     float* __restrict__ dst, int H, int W, int a, int b) {
   const int f = blockIdx.y;
-  const long long off = desc[5 * f], h64 = desc[5 * f + 1], w64 = desc[5 * f + 2], fmt64 = desc[5 * f + 4];
-  const int flip = desc[5 * f + 3] != 0;
-  bool valid = format_frame_valid(off, h64, w64, fmt64, src_bytes);
+  Surface sf{};
+  if constexpr (kSurf) sf = load_surface(desc + 10 * f);
+  const long long off = kSurf ? sf.off : desc[5 * f], h64 = kSurf ? sf.h : desc[5 * f + 1];
+  const long long w64 = kSurf ? sf.w : desc[5 * f + 2], fmt64 = kSurf ? sf.fmt : desc[5 * f + 4];
+  const int flip = kSurf ? sf.flip : desc[5 * f + 3] != 0;
+  bool valid = kSurf ? sf.valid : format_frame_valid(off, h64, w64, fmt64, src_bytes);
   const LetterboxGeom geo = letterbox_geom(valid ? (int)h64 : 1, valid ? (int)w64 : 1, a, b);
   valid = valid && geo.ok;
   const int h = valid ? (int)h64 : 1, w = valid ? (int)w64 : 1, fmt = (int)fmt64;
@@ -265,7 +332,10 @@ __global__ __launch_bounds__(256) void image_batch_letterbox_kernel(const unsign
     r = 0.f, g = 0.f, b = 0.f;
     if (valid && (unsigned)sy < (unsigned)h && (unsigned)sx < (unsigned)w) {
       int ri, gi, bi;
-      fetch_rgb_u8(frame, h, w, fmt, sy, sx, ri, gi, bi);
+      if constexpr (kSurf)
+        fetch_rgb_u8(sf, fmt, sy, sx, ri, gi, bi);
+      else
+        fetch_rgb_u8(frame, h, w, fmt, sy, sx, ri, gi, bi);
       r = (float)ri / 255.f;
       g = (float)gi / 255.f;
       b = (float)bi / 255.f;
@@ -333,18 +403,30 @@ __device__ inline void load_bytes(const unsigned char* __restrict__ src, long lo
   }
 }
 
-__global__ __launch_bounds__(256) void image_batch_area_kernel(const unsigned char* __restrict__ src, long long src_bytes,
+// kSurf (me_image_batch_surfaces_u8_f32): desc is [n,10], one Surface per frame.  The rows of a frame are then `pitch` bytes
+// apart (the NV12 chroma rows `uv_pitch`, from `uv_off`), and the bound of the wide loads is the frame's own buffer.  A lane's
+// 16 bytes may run over the picture's last column into pitch padding or a neighbouring picture, as they run into the next row
+// of a dense frame: those column sums lie behind sx1 - sx0 in cs and the horizontal half never adds them.
+template <bool kSurf>
+__global__ __launch_bounds__(256) void image_batch_area_kernel(const unsigned char* __restrict__ src_, long long src_bytes_,
                                                                const long long* __restrict__ desc,
                                                                float* __restrict__ dst, int S) {
   __shared__ int cs[kAreaLds];   // column sums of the segment: RGB / BGR by byte of the row, YUV [channel][pixel]
   const int f = blockIdx.y, oy = blockIdx.x, t = threadIdx.x;
-  const long long off = desc[5 * f], h64 = desc[5 * f + 1], w64 = desc[5 * f + 2], fmt64 = desc[5 * f + 4];
-  const int flip = desc[5 * f + 3] != 0;
+  Surface sf{};
+  if constexpr (kSurf) sf = load_surface(desc + 10 * f);
+  const unsigned char* __restrict__ src = kSurf ? sf.base : src_;   // the loads stay inside [src, src + src_bytes)
+  const long long src_bytes = kSurf ? sf.bytes : src_bytes_;
+  const long long off = kSurf ? sf.off : desc[5 * f], h64 = kSurf ? sf.h : desc[5 * f + 1];
+  const long long w64 = kSurf ? sf.w : desc[5 * f + 2], fmt64 = kSurf ? sf.fmt : desc[5 * f + 4];
+  const int flip = kSurf ? sf.flip : desc[5 * f + 3] != 0;
   // the validity rules of image_batch_formats_kernel, and the range rule P <= 255 S.  S < 2^15 bounds h and w by 2^23
   // first, so the byte counts below are products that cannot overflow (that kernel divides instead).
   bool valid = h64 > 0 && w64 > 0 && h64 <= 255ll * S && w64 <= 255ll * S && off >= 0 && off <= src_bytes;
   const long long avail = src_bytes - off, hw = valid ? h64 * w64 : 0;
-  if (fmt64 == ME_PIXFMT_RGB || fmt64 == ME_PIXFMT_BGR)
+  if (kSurf)
+    valid = valid && sf.valid;
+  else if (fmt64 == ME_PIXFMT_RGB || fmt64 == ME_PIXFMT_BGR)
     valid = valid && 3 * hw <= avail;
   else if (fmt64 == ME_PIXFMT_NV12)
     valid = valid && (h64 & 1) == 0 && (w64 & 1) == 0 && hw + hw / 2 <= avail;
@@ -408,7 +490,7 @@ __global__ __launch_bounds__(256) void image_batch_area_kernel(const unsigned ch
         unsigned acc[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[j] = 0;
-        const long long pitch = 3ll * w;
+        const long long pitch = kSurf ? sf.pitch : 3ll * w;
         long long at = off + sy0 * pitch + 3ll * sx0 + k;
         auto add = [&](const unsigned (&v)[4]) {
 #pragma unroll
@@ -460,7 +542,7 @@ __global__ __launch_bounds__(256) void image_batch_area_kernel(const unsigned ch
           acc[j] += r, acc[8 + j] += g, acc[16 + j] += b;
         };
         if (fmt == ME_PIXFMT_YUYV) {   // rows of Y0 U Y1 V
-          const long long pitch = 2ll * w;
+          const long long pitch = kSurf ? sf.pitch : 2ll * w;
           long long at = off + sy0 * pitch + 2ll * (sx0 + k);
           auto rows = [&](auto wide) {
             for (int sy = sy0; sy < sy1; ++sy, at += pitch) {
@@ -479,12 +561,14 @@ __global__ __launch_bounds__(256) void image_batch_area_kernel(const unsigned ch
           else
             rows(std::false_type{});
         } else {                       // NV12: Y plane [h,w], then the interleaved UV plane [h/2,w]
-          const long long luma = off + (long long)sx0 + k, chroma = luma + (long long)h * w;
+          const long long luma = off + (long long)sx0 + k;
+          const long long chroma = kSurf ? sf.uv_off + (long long)sx0 + k : luma + (long long)h * w;
+          const long long pitch = kSurf ? sf.pitch : (long long)w, uv_pitch = kSurf ? sf.uv_pitch : (long long)w;
           auto rows = [&](auto wide) {
             for (int sy = sy0; sy < sy1; ++sy) {
               unsigned y[2], uv[2];
-              load_bytes<8, decltype(wide)::value>(src, luma + (long long)sy * w, src_bytes, y);
-              load_bytes<8, decltype(wide)::value>(src, chroma + (long long)(sy >> 1) * w, src_bytes, uv);
+              load_bytes<8, decltype(wide)::value>(src, luma + sy * pitch, src_bytes, y);
+              load_bytes<8, decltype(wide)::value>(src, chroma + (sy >> 1) * uv_pitch, src_bytes, uv);
 #pragma unroll
               for (int p = 0; p < 4; ++p) {
                 const unsigned c = (uv[p >> 1] >> (16 * (p & 1))) & 0xffffu, yy = (y[p >> 1] >> (16 * (p & 1))) & 0xffffu;
@@ -493,7 +577,8 @@ __global__ __launch_bounds__(256) void image_batch_area_kernel(const unsigned ch
               }
             }
           };
-          if (chroma + (long long)((sy1 - 1) >> 1) * w + 8 <= src_bytes)   // (the luma plane lies in front of it)
+          // (the luma plane of a dense frame lies in front of its chroma plane; a surface's planes lie anywhere)
+          if ((!kSurf || luma + (sy1 - 1) * pitch + 8 <= src_bytes) && chroma + ((sy1 - 1) >> 1) * uv_pitch + 8 <= src_bytes)
             rows(std::true_type{});
           else
             rows(std::false_type{});
@@ -748,7 +833,7 @@ int me_image_batch_letterbox_u8_f32(const uint8_t* src, int64_t src_bytes, const
   int tiles = (int)me::ceil_div((int64_t)height * width, per_block);
   if (tiles > 1024) tiles = 1024;
   const int g = me::gcd_i32(height, width);
-  hipLaunchKernelGGL(image_batch_letterbox_kernel, dim3(tiles, n), dim3(256), 0, (hipStream_t)stream, src,
+  hipLaunchKernelGGL(image_batch_letterbox_kernel<false>, dim3(tiles, n), dim3(256), 0, (hipStream_t)stream, src,
                      (long long)src_bytes, reinterpret_cast<const long long*>(desc), dst, height, width, height / g, width / g);
   return me::check_launch("image_batch_letterbox_kernel");
 }
@@ -761,9 +846,35 @@ int me_image_batch_area_u8_f32(const uint8_t* src, int64_t src_bytes, const int6
              "me_image_batch_area_u8_f32: bad n / size / src_bytes");
   ME_REQUIRE((long long)size * size < (1ll << 30), ME_E_TOOBIG, "me_image_batch_area_u8_f32: output too large");
   ME_REQUIRE((size & 3) != 0 || me::aligned16(dst), ME_E_ALIGN, "me_image_batch_area_u8_f32: dst not 16-byte aligned");
-  hipLaunchKernelGGL(image_batch_area_kernel, dim3(size, n), dim3(256), 0, (hipStream_t)stream, src, (long long)src_bytes,
+  hipLaunchKernelGGL(image_batch_area_kernel<false>, dim3(size, n), dim3(256), 0, (hipStream_t)stream, src, (long long)src_bytes,
                      reinterpret_cast<const long long*>(desc), dst, size);
   return me::check_launch("image_batch_area_kernel");
+}
+
+int me_image_batch_surfaces_u8_f32(const int64_t* desc, int32_t n, float* dst, int32_t height, int32_t width, int32_t resize,
+                                   void* stream) {
+  if (n == 0) return 0;
+  ME_REQUIRE(desc && dst, ME_E_NULLPTR, "me_image_batch_surfaces_u8_f32: null pointer");
+  ME_REQUIRE(n > 0 && n <= 65535 && height > 0 && width > 0, ME_E_BADARG, "me_image_batch_surfaces_u8_f32: bad n / height / width");
+  ME_REQUIRE(resize == 0 || resize == 1, ME_E_BADARG, "me_image_batch_surfaces_u8_f32: resize %d is neither 0 (nearest) nor 1 (area)",
+             resize);
+  ME_REQUIRE(resize == 0 || height == width, ME_E_BADARG,
+             "me_image_batch_surfaces_u8_f32: the area resize has no rectangular form (%d x %d)", height, width);
+  ME_REQUIRE((long long)height * width < (1ll << 30), ME_E_TOOBIG, "me_image_batch_surfaces_u8_f32: output too large");
+  ME_REQUIRE((width & 3) != 0 || me::aligned16(dst), ME_E_ALIGN, "me_image_batch_surfaces_u8_f32: dst not 16-byte aligned");
+  const long long* d = reinterpret_cast<const long long*>(desc);
+  if (resize == 1) {
+    hipLaunchKernelGGL(image_batch_area_kernel<true>, dim3(height, n), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned char*)nullptr, 0ll, d, dst, height);
+    return me::check_launch("image_batch_area_kernel");
+  }
+  const int per_block = (width & 3) == 0 ? kBatchPix : 256;
+  int tiles = (int)me::ceil_div((int64_t)height * width, per_block);
+  if (tiles > 1024) tiles = 1024;
+  const int g = me::gcd_i32(height, width);
+  hipLaunchKernelGGL(image_batch_letterbox_kernel<true>, dim3(tiles, n), dim3(256), 0, (hipStream_t)stream,
+                     (const unsigned char*)nullptr, 0ll, d, dst, height, width, height / g, width / g);
+  return me::check_launch("image_batch_letterbox_kernel");
 }
 
 int me_radar_heatmap_f32(const double* points, const int32_t* offsets, const int32_t* sizes, int32_t n,

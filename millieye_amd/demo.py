@@ -30,8 +30,8 @@ import torch
 
 from . import hip
 from .radar_proposals import DeviceRadarProposals, RadarProposalGenerator
-from .utils.datasets import (StagedImages, StagedRadarMaps, StagedRaggedImages, _pad_amounts, picture_hw, pixel_format_names,
-                             resize_mode)
+from .utils.datasets import (FrameSurface, StagedImages, StagedRadarMaps, StagedRaggedImages, StagedSurfaces, _pad_amounts,
+                             picture_hw, pixel_format_names, resize_mode)
 from .utils.utils import box_ops, canvas_size, letterbox_geometry, rescale_boxes, rescale_scalars
 
 __all__ = ["mode_selection", "radar_boxes_for_network", "prepare_streams", "FrameFuser", "MultiStreamFuser"]
@@ -85,6 +85,29 @@ def radar_boxes_for_network(xyxy_pixels, frame_hw, canvas=None):
     return out
 
 
+def _fuser_surface(frame, pixel_format, what):
+    """A frame of a step that reads surfaces (``utils.datasets.FrameSurface``) as the surface a fuser may take: a surface is
+    checked - its format is the stream's, and it is a whole picture: the radar chain projects into the full frame, so a
+    cropped camera picture would no longer line up with the radar boxes and maps - and a frame tensor in ``pixel_format``
+    (``None``: RGB) is wrapped, as a view where its strides allow it."""
+    if isinstance(frame, FrameSurface):
+        if pixel_format is not None and frame.pixel_format != pixel_format:
+            raise hip.MeError(f"{what}: the surface holds {frame.pixel_format}, the stream's pixel_format is {pixel_format}")
+        if tuple(frame.origin) != (0, 0):
+            raise hip.MeError(f"{what}: a cropped surface (origin {tuple(frame.origin)}) would not line up with the radar "
+                              "geometry - the fusers take whole pictures")
+        return frame
+    name = pixel_format or "rgb"
+    frame = torch.as_tensor(frame)
+    h, w = picture_hw(frame, name, what)
+    if name == "nv12":   # the Y plane over the UV plane in one dense tensor
+        return FrameSurface(frame.contiguous().reshape(-1), h, w, "nv12")
+    c = int(frame.shape[2])
+    if frame.stride(2) != 1 or frame.stride(1) != c or (h > 1 and frame.stride(0) < w * c):
+        frame = frame.contiguous()
+    return FrameSurface.from_view(frame, name)
+
+
 class FrameFuser:
     """``fuser(frame_uint8_hwc, radar_frames)`` -> ``(detections [m,7], info)``; detections are rows
     ``(x1, y1, x2, y2, conf, cls_conf, cls_pred)`` in pixels of the original frame, like the demos draw them.
@@ -96,7 +119,10 @@ class FrameFuser:
     ``img_size=(H, W)`` (sides multiples of 32): the frame is letterboxed to the rectangular network input
     (``utils.utils.letterbox_geometry``, ``me_image_batch_letterbox_u8_f32``), the radar boxes are normalised per axis, the radar
     map is the dataset's resized ``(H / 16, W / 16)`` map (the raw 32 x 32 map of the square path has no rectangular form) and
-    the rows come back through the per-axis ``rescale_boxes``.  ``(S, S)`` is ``S``; ``resize="area"`` is refused."""
+    the rows come back through the per-axis ``rescale_boxes``.  ``(S, S)`` is ``S``; ``resize="area"`` is refused.
+
+    ``frame`` may be a ``utils.datasets.FrameSurface`` (a pitched or device-resident picture, read where it lies by
+    ``StagedSurfaces``); its format must be ``pixel_format`` where that is given, and a cropped surface is refused."""
 
     def __init__(self, model, calib_param, model_mode=3, img_size=416, nms_iou=0.3, dark_threshold=0.08, generator=None,
                  pixel_format=None, resize=None, **generator_kwargs):
@@ -121,11 +147,16 @@ class FrameFuser:
     # needs the device.  ``prepare`` keeps the tracker state, so it must see the frames in order.
     def prepare(self, frame, radar_frames):
         """Host half (run_mp.py:65-152 ``pre_process``): a picklable payload for :meth:`infer`."""
-        frame = torch.as_tensor(frame)
-        if self.pixel_format is not None or self.resize == "area" or self.rect:
+        if isinstance(frame, FrameSurface):
+            frame = _fuser_surface(frame, self.pixel_format, "FrameFuser")
+            h, w = frame.h, frame.w
+            img = StagedSurfaces([frame], self.img_size, resize=self.resize)
+        elif self.pixel_format is not None or self.resize == "area" or self.rect:
+            frame = torch.as_tensor(frame)
             h, w = picture_hw(frame, self.pixel_format or "rgb")
             img = StagedRaggedImages([frame], self.img_size, formats=self.pixel_format, resize=self.resize).pack()
         else:
+            frame = torch.as_tensor(frame)
             if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3:
                 raise hip.MeError(f"frame must be uint8 [h,w,3] (got {frame.dtype} {tuple(frame.shape)})")
             h, w = int(frame.shape[0]), int(frame.shape[1])
@@ -169,11 +200,25 @@ def prepare_streams(frames, radar_frames, streams, img_size=416, pack=False, pix
     ``img_size=(H, W)``: the frames are staged for the letterbox kernel (``StagedRaggedImages(size=(H, W))``).
 
     ``out`` (with ``pack=True``): the 1-D uint8 tensor the bytes are packed into (``StagedRaggedImages.pack(out=)``) - a slot of
-    the pipeline's ``handover.FrameRing``."""
+    the pipeline's ``handover.FrameRing``.
+
+    Any frame may be a ``utils.datasets.FrameSurface`` - a pitched host buffer, a picture a decoder left in device memory - in
+    place of a tensor.  A step with at least one surface stages ALL its frames through ``StagedSurfaces`` (tensors are wrapped,
+    as views where their strides allow) and one ``me_image_batch_surfaces_u8_f32`` launch; a step of tensors goes the way it
+    always went.  ``payload["hw"]`` is the surface's ``(h, w)``; a surface whose format is not the stream's ``pixel_format``,
+    a cropped surface (``origin != (0, 0)``: the radar chain projects into the full frame) and ``pack=True`` raise."""
     resize = resize_mode(resize, "prepare_streams")
     img_size = _network_input_size(img_size, "prepare_streams")
     if len(frames) != streams or len(radar_frames) != streams:
         raise hip.MeError(f"MultiStreamFuser: {len(frames)} frames / {len(radar_frames)} radar lists for {streams} streams")
+    if any(isinstance(f, FrameSurface) for f in frames):
+        if pack or out is not None:
+            raise hip.MeError("prepare_streams: pack=True packs dense frames - surfaces are not packed, and a device buffer "
+                              "does not cross a process boundary")
+        names = [None] * streams if pixel_format is None else pixel_format_names(pixel_format, streams, "stream")
+        surfaces = [_fuser_surface(f, name, f"stream {i}") for i, (f, name) in enumerate(zip(frames, names))]
+        return dict(hw=[(s.h, s.w) for s in surfaces], img=StagedSurfaces(surfaces, img_size, resize=resize),
+                    radar_frames=[list(r) for r in radar_frames])
     frames = [torch.as_tensor(f) for f in frames]
     if pixel_format is not None:
         names = pixel_format_names(pixel_format, streams, "stream")
@@ -251,7 +296,12 @@ class MultiStreamFuser:
     square path has no rectangular form), the network's radar boxes are rebuilt per axis from the device proposals
     (``DeviceRadarProposals.letterbox_boxes``: two launches and one more small copy per step, for the counts the sub-batch
     gather and ``info["radar_boxes"]`` use) and both tails rescale per axis - the tail kernel is unchanged, only its six
-    scalars per stream differ.  ``split="frame_modes"`` and ``resize="area"`` are refused with a rectangular size."""
+    scalars per stream differ.  ``split="frame_modes"`` and ``resize="area"`` are refused with a rectangular size.
+
+    Any stream's frame may be a ``utils.datasets.FrameSurface`` - a pitched host buffer, a picture a decoder left in device
+    memory - in place of a tensor: the step's frames are then read where they lie (``StagedSurfaces``, one
+    ``me_image_batch_surfaces_u8_f32`` launch) and every stream's rows are ``torch.equal`` to those of the dense copies
+    (:func:`prepare_streams`).  Everything behind the input launch is the same."""
 
     def __init__(self, model, calib_params, streams, model_mode=3, img_size=416, nms_iou=0.3, dark_threshold=0.08,
                  tail="device", split="forwards", pixel_format=None, resize=None, **generator_kwargs):

@@ -238,6 +238,8 @@ SIGNATURES = {
                                        C.c_void_p]),
     "me_image_batch_letterbox_u8_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                                   C.c_int32, C.c_void_p]),
+    "me_image_batch_surfaces_u8_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.c_void_p]),
     "me_radar_heatmap_rect_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                             C.c_int32, C.c_void_p]),
     "me_radar_boxes_letterbox_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,

@@ -29,7 +29,7 @@ from .. import hip
 from .utils import canvas_hw, canvas_size
 
 __all__ = ["MyDataset", "StagedImages", "StagedRaggedImages", "StagedRadarMaps", "obtain_bboxs", "PIXEL_FORMATS",
-           "picture_hw", "RESIZE_MODES", "resize_mode"]
+           "picture_hw", "RESIZE_MODES", "resize_mode", "FrameSurface", "StagedSurfaces"]
 
 _SCENES = ["0", "1", "2", "3", "4"]
 
@@ -351,6 +351,225 @@ class StagedRaggedImages(StagedImages):
         name = dtype if isinstance(dtype, str) else f"{getattr(dtype, '__module__', '')}.{getattr(dtype, '__name__', '')}"
         if name != "torch.cuda.FloatTensor":
             raise hip.MeError(f"StagedRaggedImages.type({dtype!r}): the batch is built on the GPU as torch.cuda.FloatTensor")
+        return self.to("cuda")
+
+
+_ROW_BYTES_PER_PIXEL = {"rgb": 3, "bgr": 3, "yuyv": 2, "nv12": 1}   # bytes of plane 0 per pixel of a row
+
+
+class FrameSurface:
+    """A picture where it lies: ``h x w`` pixels in ``pixel_format`` inside ``buffer`` (a 1-D contiguous uint8 torch tensor on
+    the CPU or on a CUDA device), its first byte at ``offset``, consecutive rows ``pitch`` bytes apart (``None``: dense rows).
+    NV12 has its interleaved UV plane at ``uv_offset`` (``None``: ``offset + h * pitch``, right behind the Y plane) with rows
+    ``uv_pitch`` bytes apart (``None``: ``pitch``).  This is what a V4L2 buffer (``bytesperline``), a hardware decoder (aligned
+    pitch, UV plane behind an aligned height, in device memory) or a slice of a larger frame looks like;
+    :class:`StagedSurfaces` reads it without a gather into a dense tensor.
+
+    The constructor applies the validity rules of ``me_image_batch_surfaces_u8_f32`` (include/millieye_hip.h) on the host and
+    raises :class:`hip.MeError` naming the rule and the numbers.  ``origin`` is ``(x0, y0)`` of this picture in the picture the
+    surface was first built on: ``(0, 0)`` at construction, accumulated by :meth:`crop`.
+
+    A surface on a CUDA buffer does not pickle (a device buffer does not cross a process boundary)."""
+
+    origin = (0, 0)
+
+    def __init__(self, buffer, h, w, pixel_format="rgb", offset=0, pitch=None, uv_offset=None, uv_pitch=None):
+        if not isinstance(pixel_format, str) or pixel_format not in PIXEL_FORMATS:
+            raise hip.MeError(f"FrameSurface: unknown pixel format {pixel_format!r} (one of {', '.join(PIXEL_FORMATS)})")
+        if not isinstance(buffer, torch.Tensor) or buffer.dtype != torch.uint8 or buffer.dim() != 1 \
+                or not buffer.is_contiguous() or buffer.device.type not in ("cpu", "cuda"):
+            raise hip.MeError("FrameSurface: buffer must be a 1-D contiguous uint8 torch tensor on the CPU or a CUDA device (got "
+                              f"{getattr(buffer, 'dtype', type(buffer).__name__)} {tuple(getattr(buffer, 'shape', ()))})")
+        self.buffer, self.pixel_format = buffer, pixel_format
+        self.h, self.w, self.offset = int(h), int(w), int(offset)
+        nv12 = pixel_format == "nv12"
+        row = _ROW_BYTES_PER_PIXEL[pixel_format] * self.w
+        self.pitch = row if pitch is None else int(pitch)
+        self.uv_offset = (self.offset + self.h * self.pitch if uv_offset is None else int(uv_offset)) if nv12 else 0
+        self.uv_pitch = (self.pitch if uv_pitch is None else int(uv_pitch)) if nv12 else 0
+        self._check(row)
+
+    def _check(self, row):
+        h, w, off, pitch, nbytes = self.h, self.w, self.offset, self.pitch, int(self.buffer.numel())
+        what = f"FrameSurface ({self.pixel_format} {h} x {w})"
+        if nbytes <= 0 or self.buffer.data_ptr() == 0:
+            raise hip.MeError(f"{what}: the buffer is empty (bytes > 0 and base != 0 are required)")
+        if not (1 <= h <= 1 << 30 and 1 <= w <= 1 << 30):
+            raise hip.MeError(f"{what}: 1 <= h, w <= 2^30 is required")
+        if self.pixel_format == "nv12" and (h % 2 or w % 2):
+            raise hip.MeError(f"{what}: nv12 needs h and w even")
+        if self.pixel_format == "yuyv" and w % 2:
+            raise hip.MeError(f"{what}: yuyv needs w even")
+        if pitch < row:
+            raise hip.MeError(f"{what}: pitch {pitch} is below the row's {row} bytes (pitch >= row; no negative pitches)")
+        if not 0 <= off <= nbytes - row:
+            raise hip.MeError(f"{what}: offset {off} is outside [0, bytes - row] = [0, {nbytes} - {row}]")
+        if h - 1 > (nbytes - row - off) // pitch:
+            raise hip.MeError(f"{what}: the last row ends at byte {off + (h - 1) * pitch + row} of a buffer of {nbytes} "
+                              f"(offset {off}, pitch {pitch})")
+        if self.pixel_format == "nv12":
+            uv_off, uv_pitch = self.uv_offset, self.uv_pitch
+            if uv_pitch < w:
+                raise hip.MeError(f"{what}: uv_pitch {uv_pitch} is below the chroma row's {w} bytes (uv_pitch >= w)")
+            if not 0 <= uv_off <= nbytes - w:
+                raise hip.MeError(f"{what}: uv_offset {uv_off} is outside [0, bytes - w] = [0, {nbytes} - {w}]")
+            if h // 2 - 1 > (nbytes - w - uv_off) // uv_pitch:
+                raise hip.MeError(f"{what}: the last chroma row ends at byte {uv_off + (h // 2 - 1) * uv_pitch + w} of a buffer "
+                                  f"of {nbytes} (uv_offset {uv_off}, uv_pitch {uv_pitch})")
+
+    @property
+    def row_bytes(self):
+        return _ROW_BYTES_PER_PIXEL[self.pixel_format] * self.w
+
+    def span(self):
+        """``(lo, hi)``: the byte range of the buffer the picture's rows touch (both planes of NV12)."""
+        lo, hi = self.offset, self.offset + (self.h - 1) * self.pitch + self.row_bytes
+        if self.pixel_format == "nv12":
+            lo = min(lo, self.uv_offset)
+            hi = max(hi, self.uv_offset + (self.h // 2 - 1) * self.uv_pitch + self.w)
+        return lo, hi
+
+    def row(self, base, nbytes, rebase=0, flip=False):
+        """The surface's row of the ``[n,10]`` descriptor when ``nbytes`` of its buffer, from byte ``rebase`` on, lie at the
+        device address ``base``."""
+        return [int(base), int(nbytes), self.offset - rebase, self.h, self.w, int(bool(flip)), PIXEL_FORMATS[self.pixel_format],
+                self.pitch, self.uv_offset - rebase if self.pixel_format == "nv12" else 0, self.uv_pitch]
+
+    def crop(self, x0, y0, cw, ch):
+        """The ``ch x cw`` region at column ``x0``, row ``y0`` as a new surface on the same buffer: offset arithmetic, no copy.
+        YUYV needs ``x0`` and ``cw`` even, NV12 all four (whole chroma samples)."""
+        x0, y0, cw, ch = int(x0), int(y0), int(cw), int(ch)
+        what = f"FrameSurface.crop({x0}, {y0}, {cw}, {ch}) of {self.pixel_format} {self.h} x {self.w}"
+        if x0 < 0 or y0 < 0 or cw < 1 or ch < 1 or x0 + cw > self.w or y0 + ch > self.h:
+            raise hip.MeError(f"{what}: the region does not lie inside the picture")
+        if self.pixel_format == "yuyv" and (x0 % 2 or cw % 2):
+            raise hip.MeError(f"{what}: yuyv needs x0 and the width even")
+        if self.pixel_format == "nv12" and (x0 % 2 or y0 % 2 or cw % 2 or ch % 2):
+            raise hip.MeError(f"{what}: nv12 needs x0, y0, the width and the height even")
+        nv12 = self.pixel_format == "nv12"
+        out = FrameSurface(self.buffer, ch, cw, self.pixel_format,
+                           self.offset + y0 * self.pitch + _ROW_BYTES_PER_PIXEL[self.pixel_format] * x0, self.pitch,
+                           self.uv_offset + (y0 // 2) * self.uv_pitch + x0 if nv12 else None, self.uv_pitch if nv12 else None)
+        out.origin = (self.origin[0] + x0, self.origin[1] + y0)
+        return out
+
+    @classmethod
+    def from_view(cls, tensor, pixel_format="rgb"):
+        """The surface of a uint8 ``[h,w,3]`` (``"rgb"`` / ``"bgr"``) or ``[h,w,2]`` (``"yuyv"``) torch tensor or numpy array
+        whose innermost two dimensions are dense and whose row stride is at least the row's bytes - a slice
+        ``full[y0:y1, x0:x1]``, a V4L2 buffer viewed with its ``bytesperline`` - built on the tensor's storage without a copy.
+        Any other stride pattern raises and names the strides; so does ``"nv12"`` (two planes are not one view)."""
+        if pixel_format == "nv12":
+            raise hip.MeError("FrameSurface.from_view: nv12 has two planes, which one view cannot describe - build the "
+                              "FrameSurface with uv_offset / uv_pitch")
+        h, w = picture_hw(tensor, pixel_format, "FrameSurface.from_view")
+        t = torch.as_tensor(tensor)
+        c, strides = int(t.shape[2]), tuple(int(s) for s in t.stride())
+        if strides[2] != 1 or strides[1] != c or (h > 1 and strides[0] < w * c):
+            raise hip.MeError(f"FrameSurface.from_view: strides {strides} of a {tuple(t.shape)} view are not (pitch >= {w * c}, "
+                              f"{c}, 1)")
+        storage = t.untyped_storage()
+        buffer = torch.empty(0, dtype=torch.uint8, device=t.device).set_(storage, 0, (storage.nbytes(),), (1,))
+        return cls(buffer, h, w, pixel_format, int(t.storage_offset()), strides[0] if h > 1 else w * c)
+
+    def __getstate__(self):
+        if self.buffer.device.type != "cpu":
+            raise hip.MeError(f"FrameSurface: a surface on a {self.buffer.device} buffer does not pickle (a device buffer does "
+                              "not cross a process boundary)")
+        return self.__dict__
+
+
+class StagedSurfaces:
+    """A batch of :class:`FrameSurface` waiting for ``.to(device)``: the sibling of :class:`StagedRaggedImages` that reads the
+    frames where they lie.  ``to("cuda")`` uploads, per distinct CPU buffer and in one ``non_blocking`` copy, the byte span from
+    the lowest to the highest byte any of its surfaces touches (a pitched V4L2 buffer goes up as it is, a region of interest
+    takes only its rows along), uploads nothing for CUDA buffers, and makes one ``me_image_batch_surfaces_u8_f32`` launch with a
+    ``[n,10]`` descriptor per frame: ``[n,3,size,size]`` (``[n,3,H,W]`` for ``size=(H, W)``), every frame bit-identical to what
+    :class:`StagedRaggedImages` gives on its pixels copied into a dense frame.  ``flips``, ``resize`` and ``size`` mean what they
+    mean there; ``resize="area"`` with a rectangular size raises here as well.
+
+    The surfaces' buffers must stay alive until the launch has run; tensors used on the current stream do (torch's allocator
+    is stream-ordered)."""
+
+    def __init__(self, surfaces, size, flips=None, resize=None):
+        self.surfaces = list(surfaces)
+        size = canvas_size(size, "StagedSurfaces size")
+        self.size = size
+        self.resize = resize_mode(resize, "StagedSurfaces")
+        if isinstance(size, tuple) and self.resize == "area":
+            raise hip.MeError(f"StagedSurfaces: resize='area' has no rectangular form (size {size[0]} x {size[1]})")
+        self.flips = [bool(f) for f in flips] if flips is not None else [False] * len(self.surfaces)
+        if len(self.flips) != len(self.surfaces):
+            raise hip.MeError(f"StagedSurfaces: {len(self.flips)} flips for {len(self.surfaces)} surfaces")
+        for i, s in enumerate(self.surfaces):
+            if not isinstance(s, FrameSurface):
+                raise hip.MeError(f"StagedSurfaces: surface {i} is a {type(s).__name__}, not a FrameSurface")
+            if self.resize == "area" and max(s.h, s.w) > 255 * size:
+                raise hip.MeError(f"surface {i}: {s.h} x {s.w} is beyond the area resize's range max(h, w) <= 255 * size = "
+                                  f"{255 * size}")
+        self.shape = torch.Size((len(self.surfaces), 3) + canvas_hw(size))
+        self.dtype = torch.float32
+
+    def __len__(self):
+        return len(self.surfaces)
+
+    def plan(self):
+        """The host half of :meth:`to`, without a GPU: ``(spans, where)`` - ``spans`` lists ``[buffer, lo, hi]`` per distinct CPU
+        buffer, the byte range its surfaces touch; ``where[i]`` is the span surface ``i`` reads from, ``None`` for a surface on
+        a CUDA buffer."""
+        spans, where, index = [], [], {}
+        for s in self.surfaces:
+            if s.buffer.device.type != "cpu":
+                where.append(None)
+                continue
+            key, (lo, hi) = (s.buffer.data_ptr(), int(s.buffer.numel())), s.span()
+            if key not in index:
+                index[key] = len(spans)
+                spans.append([s.buffer, lo, hi])
+            else:
+                span = spans[index[key]]
+                span[1], span[2] = min(span[1], lo), max(span[2], hi)
+            where.append(index[key])
+        return spans, where
+
+    def descriptor(self, addresses):
+        """The ``[n,10]`` int64 descriptor when span ``k`` of :meth:`plan` lies at the device address ``addresses[k]``: the
+        surfaces of a CPU buffer are rebased onto its span, a CUDA buffer is named as it is."""
+        spans, where = self.plan()
+        rows = []
+        for s, k, flip in zip(self.surfaces, where, self.flips):
+            if k is None:
+                rows.append(s.row(s.buffer.data_ptr(), s.buffer.numel(), 0, flip))
+            else:
+                rows.append(s.row(addresses[k], spans[k][2] - spans[k][1], spans[k][1], flip))
+        return torch.tensor(rows, dtype=torch.int64).reshape(-1, 10)
+
+    def to(self, device, *_, **__):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise hip.MeError("StagedSurfaces.to(): the batch is assembled by the HIP library - CUDA device required")
+        n = len(self.surfaces)
+        out = torch.empty(tuple(self.shape), device=device, dtype=torch.float32)
+        if n == 0:
+            return out
+        for i, s in enumerate(self.surfaces):
+            if s.buffer.device.type == "cuda" and s.buffer.device != out.device:
+                raise hip.MeError(f"StagedSurfaces.to({out.device}): surface {i} lies on {s.buffer.device}")
+        spans, _ = self.plan()
+        uploads = [buffer[lo:hi].to(device, non_blocking=True) for buffer, lo, hi in spans]
+        d_desc = self.descriptor([u.data_ptr() for u in uploads]).pin_memory().to(device, non_blocking=True)
+        height, width = canvas_hw(self.size)
+        hip.check(hip.lib().me_image_batch_surfaces_u8_f32(d_desc.data_ptr(), n, out.data_ptr(), height, width,
+                                                           int(self.resize == "area"), hip.stream_ptr()),
+                  "me_image_batch_surfaces_u8_f32")
+        return out
+
+    def type(self, dtype=None, non_blocking=False, **__):
+        if dtype is None:
+            return "torch.cuda.FloatTensor"
+        name = dtype if isinstance(dtype, str) else f"{getattr(dtype, '__module__', '')}.{getattr(dtype, '__name__', '')}"
+        if name != "torch.cuda.FloatTensor":
+            raise hip.MeError(f"StagedSurfaces.type({dtype!r}): the batch is built on the GPU as torch.cuda.FloatTensor")
         return self.to("cuda")
 
 
