@@ -944,6 +944,58 @@ int me_frame_means_f32(const float* imgs, int32_t n, int64_t elems_per_frame, fl
 int me_frame_modes_f32(const float* imgs, int32_t n, int64_t elems_per_frame, double threshold, float* means, int32_t* modes,
                        void* stream);
 
+/* ---- track ids for the detections of every stream (csrc/box_tracks.hip) ----------------------------------------------
+ * me_box_tracks_f64: one SORT-shaped tracker per stream (Bewley et al. 2016: constant-velocity Kalman filter on
+ *   (cx, cy, w, h) and their velocities, IoU association solved exactly, births, deaths, the min_hits rule) behind
+ *   me_stream_tail_f32, in one launch, one workgroup per stream, float64 without contraction.  The specification is
+ *   millieye_amd/detection_tracks.py:DetectionTracker.
+ *   tail_out: the device output buffer of me_stream_tail_f32 exactly as that call left it (for `streams` streams and `m` rows):
+ *   stream s's detections are its kept rows (x1, y1, x2, y2, conf, cls_score, cls_pred), in kept order.  No host read-back in
+ *   between.  state: me_box_tracks_state_bytes(streams) bytes, 16-byte aligned, zero = no tracks, first id 1
+ *   (me_box_tracks_reset).
+ *   Per step and stream: frame_count += 1; every track is predicted (a width or height about to reach zero stops shrinking);
+ *   iou[track][detection] of the predicted boxes (0 across classes); linear_sum_assignment(-iou) (scipy's shortest augmenting
+ *   paths, ties included; transposed when tracks > detections); pairs under iou_min are dropped; matched tracks take the
+ *   Joseph-form update, unmatched detections with conf >= birth_conf become tracks (ids count up per stream), tracks with
+ *   time_since_update > max_age die, the rest keep their order.
+ *   tracks [streams, MAX_TRACKS, 10] float64: the tracks updated or born this step that have hit_streak >= min_hits (or
+ *   frame_count <= min_hits), in track order: (id, x1, y1, x2, y2, conf, cls, hit_streak, age, detection index); only the
+ *   first counts[s][1] rows of a stream are written.  counts [streams, 4] int32 = (status, rows, live tracks, frame_count).
+ *   cost [streams, MAX_TRACKS, MAX_DETS] float64 (may be NULL): the IoU matrix of the step, entries [track < tracks before
+ *   the step][detection < detections] only.  matches [streams, MAX_TRACKS] (may be NULL): the detection matched to each track
+ *   the stream had before the step, or -1; entries of those tracks only.
+ *   A stream with a status other than ME_TRACKS_OK keeps its state untouched, frame_count included, and has 0 rows; its
+ *   counts report the live tracks and the frame_count it keeps.  A set status word of tail_out gives every stream
+ *   ME_TRACKS_E_INPUT.  The call returns 0 in all these cases. */
+#define ME_TRACKS_MAX_DETS 64
+#define ME_TRACKS_MAX_TRACKS 64
+#define ME_TRACKS_ROW_COLS 10
+#define ME_TRACKS_COUNT_COLS 4
+#define ME_TRACKS_OK 0
+#define ME_TRACKS_E_DETS 1    /* more than ME_TRACKS_MAX_DETS detections                                        */
+#define ME_TRACKS_E_INPUT 2   /* a box coordinate is not finite, or tail_out is flagged or inconsistent with m  */
+#define ME_TRACKS_E_TRACKS 3  /* live tracks + births exceed ME_TRACKS_MAX_TRACKS                               */
+typedef struct me_box_tracks_desc {
+  const void* tail_out;
+  void* state;
+  double* tracks;
+  int32_t* counts;
+  double* cost;        /* may be NULL */
+  int32_t* matches;    /* may be NULL */
+  double iou_min, birth_conf;
+  int32_t m, streams, max_age, min_hits;
+} me_box_tracks_desc;
+/* which = 0 MAX_DETS, 1 MAX_TRACKS, 2 ROW_COLS, 3 COUNT_COLS, 4 bytes of a stream's state header (int32 frame_count, live
+ * tracks, ids given out so far, padding), 5 bytes of one track (double x[8] = (cx, cy, w, h, vcx, vcy, vw, vh); double
+ * P[4][4]: for each of the four coordinates the 2 x 2 covariance block of (coordinate, its velocity), row-major - every other
+ * entry of the 8 x 8 matrix is exactly zero; int32 id; float cls, conf; int32 time_since_update, hits, hit_streak, age, det);
+ * -1 otherwise.  A stream's state is the header followed by MAX_TRACKS tracks. */
+int32_t me_box_tracks_capacity(int32_t which);
+int64_t me_box_tracks_state_bytes(int32_t streams);
+/* zero the state of one stream (which >= 0) or of all of them (which < 0); stream-ordered */
+int me_box_tracks_reset(void* state, int32_t streams, int32_t which, void* stream);
+int me_box_tracks_f64(const me_box_tracks_desc* d, void* stream);
+
 /* ---- evaluation tail -----------------------------------------------------------------
  * get_batch_statistics (module3_our_dataset/utils/utils.py:185-236) for one batch, on the output rows of
  * Network.forward as they are: rows [m,cols] = (image_i, x1,y1,x2,y2, ..., class_pred last), targets [q,6] =
@@ -1069,7 +1121,7 @@ int me_adam_step_f32(const me_adam_desc* d, void* stream);
 int32_t me_adam_chunk(void);
 
 /* sizes of the descriptor structs, so a binding can assert its mirror layout */
-int32_t me_sizeof(int32_t which); /* 0 conv, 1 pool, 2 yolo, 3 nms, 4 heads, 5 heads_weights, 6 conv16, 7 pack, 8 bneck16, 9 adam, 10 radar, 11 nms_python, 12 yolo_rect */
+int32_t me_sizeof(int32_t which); /* 0 conv, 1 pool, 2 yolo, 3 nms, 4 heads, 5 heads_weights, 6 conv16, 7 pack, 8 bneck16, 9 adam, 10 radar, 11 nms_python, 12 yolo_rect, 13 box_tracks */
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,7 @@ int32_t me_sizeof(int32_t which) {
     case 10: return (int32_t)sizeof(me_radar_desc);
     case 11: return (int32_t)sizeof(me_nms_python_desc);
     case 12: return (int32_t)sizeof(me_yolo_rect_desc);
+    case 13: return (int32_t)sizeof(me_box_tracks_desc);
     default: return -1;
   }
 }

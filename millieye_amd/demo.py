@@ -301,10 +301,23 @@ class MultiStreamFuser:
     Any stream's frame may be a ``utils.datasets.FrameSurface`` - a pitched host buffer, a picture a decoder left in device
     memory - in place of a tensor: the step's frames are then read where they lie (``StagedSurfaces``, one
     ``me_image_batch_surfaces_u8_f32`` launch) and every stream's rows are ``torch.equal`` to those of the dense copies
-    (:func:`prepare_streams`).  Everything behind the input launch is the same."""
+    (:func:`prepare_streams`).  Everything behind the input launch is the same.
+
+    ``tracks``: ``None`` (default) - nothing below happens.  ``True`` or a dict of ``detection_tracks.DetectionTracker``
+    parameters (``max_age``, ``min_hits``, ``iou_min``, ``birth_conf``): every stream's detections get track ids from a tracker
+    of its own on the device (``detection_tracks.DeviceDetectionTracks``, one launch behind the tail's, reading the tail's
+    output buffer where it lies; ``hip.stream_tail_tracks``).  Every stream's ``info`` gains ``"tracks"``, a ``[k,10]`` float64
+    numpy array ``(id, x1, y1, x2, y2, conf, cls, hit_streak, age, det)`` - ``det`` is the row of the stream's returned
+    detections behind the track - and ``"track_status"`` (0, or a ``hip.TRACKS_E_*`` word: that stream's tracker refused the
+    step, kept its state and has no rows).  The detection rows are ``torch.equal`` to those without tracking and the step has no
+    more device-to-host copies; its tail takes 0.02 - 0.07 ms longer (S = 1 .. 32, ``profiles/box_tracks_latency.txt``), where
+    S host trackers take 0.2 - 7.3 ms.  It needs ``tail="device"``.  :attr:`tracker` is the device tracker
+    (``tracker.reset(stream)`` forgets one stream's tracks).  :meth:`advance` does not touch it: a step that ``pipeline.FusionPipeline`` skips has no
+    detections, so it does not age the tracks - ``max_age`` counts the steps that were inferred, not the frames that
+    arrived."""
 
     def __init__(self, model, calib_params, streams, model_mode=3, img_size=416, nms_iou=0.3, dark_threshold=0.08,
-                 tail="device", split="forwards", pixel_format=None, resize=None, **generator_kwargs):
+                 tail="device", split="forwards", pixel_format=None, resize=None, tracks=None, **generator_kwargs):
         self.model, self.model_mode, self.streams = model, model_mode, int(streams)
         self.img_size = _network_input_size(img_size, "MultiStreamFuser")
         self.rect = isinstance(self.img_size, tuple)
@@ -326,6 +339,16 @@ class MultiStreamFuser:
             raise hip.MeError(f"MultiStreamFuser: resize='area' has no rectangular form (img_size {self.img_size[0]} x "
                               f"{self.img_size[1]})")
         self.tail = tail
+        if tracks is not None and tracks is not False:
+            if tail != "device":
+                raise hip.MeError("MultiStreamFuser: tracks need tail='device' (the tracker reads the device tail's output buffer)")
+            if tracks is not True and not isinstance(tracks, dict):
+                raise hip.MeError(f"MultiStreamFuser: tracks must be None, True or a dict of tracker parameters (got {tracks!r})")
+            self.track_params = {} if tracks is True else dict(tracks)
+        else:
+            self.track_params = None
+        self._tracker = None
+        self._step_tracks = None       # (rows per stream, status per stream) of the step being inferred
         self.calib_params, self.generator_kwargs = calib_params, generator_kwargs
         self._device = getattr(model, "device", None)
         self._generator = None
@@ -343,6 +366,14 @@ class MultiStreamFuser:
         if self._generator is None:
             self._generator = DeviceRadarProposals(self.calib_params, self.streams, device=self.device, **self.generator_kwargs)
         return self._generator
+
+    @property
+    def tracker(self):
+        """The device tracker of ``tracks=`` (built on first use, like :attr:`generator`); ``None`` without tracking."""
+        if self._tracker is None and self.track_params is not None:
+            from .detection_tracks import DeviceDetectionTracks
+            self._tracker = DeviceDetectionTracks(self.streams, device=self.device, **self.track_params)
+        return self._tracker
 
     def __call__(self, frames, radar_frames):
         return self.infer(self.prepare(frames, radar_frames))
@@ -427,6 +458,9 @@ class MultiStreamFuser:
             r = per_stream[s]
             result.append((r, dict(mode=modes[s], proposals=proposals[s, :int(counts[s, 7])].copy(),
                                    radar_boxes=int(counts[s, 4]), points=int(counts[s, 1]))))
+            if self._step_tracks is not None:
+                result[-1][1].update(tracks=self._step_tracks[0][s], track_status=int(self._step_tracks[1][s]))
+        self._step_tracks = None
         return result
 
     def _tail(self, rows, hws):
@@ -436,6 +470,11 @@ class MultiStreamFuser:
             key = tuple(hws)
             if self._scalars[0] != key:   # the frame sizes rarely change: their scalars stay on the device
                 self._scalars = (key, rescale_scalars(self.img_size, hws).to(rows.device))
+            if self.track_params is not None:
+                per_stream, _counts, tracks, status = hip.stream_tail_tracks(
+                    rows.to(torch.float32).contiguous(), self.streams, self._scalars[1], self.nms_iou, self.tracker)
+                self._step_tracks = (tracks, status)
+                return per_stream
             return hip.stream_tail(rows.to(torch.float32).contiguous(), self.streams, self._scalars[1], self.nms_iou)[0]
         per_stream = self._second_nms(rows)
         for s, r in enumerate(per_stream):

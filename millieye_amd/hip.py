@@ -189,6 +189,21 @@ RADAR_STATE_HEADER_BYTES, RADAR_TRACK_BYTES = 64, 768
 RADAR_STATUS = {1: ("points that pass the filter", RADAR_MAX_POINTS), 2: ("clusters", RADAR_MAX_CLUSTERS),
                 3: ("tracks", RADAR_MAX_TRACKS), 4: ("finite association costs", 0)}
 
+
+class BoxTracksDesc(C.Structure):
+    """me_box_tracks_desc: the per-stream detection tracker behind the stream tail (csrc/box_tracks.hip)."""
+    _fields_ = [(name, C.c_void_p) for name in ("tail_out", "state", "tracks", "counts", "cost", "matches")] + [
+        ("iou_min", C.c_double), ("birth_conf", C.c_double),
+        ("m", C.c_int32), ("streams", C.c_int32), ("max_age", C.c_int32), ("min_hits", C.c_int32),
+    ]
+
+
+# capacities / status words of me_box_tracks_f64 (include/millieye_hip.h) and the layout of its state; load() checks them
+# against the library (me_box_tracks_capacity)
+TRACKS_MAX_DETS, TRACKS_MAX_TRACKS, TRACKS_ROW_COLS, TRACKS_COUNT_COLS = 64, 64, 10, 4
+TRACKS_STATE_HEADER_BYTES, TRACKS_TRACK_BYTES = 32, 224
+TRACKS_OK, TRACKS_E_DETS, TRACKS_E_INPUT, TRACKS_E_TRACKS = 0, 1, 2, 3   # more than 64 detections / bad input / more than 64 tracks
+
 ADAM_MAX_TENSORS = 64
 
 # me_conv_wgrad_form (include/millieye_hip.h): ME_WGRAD_FORM_* / ME_WGRAD_REDUCE_* by name
@@ -213,7 +228,7 @@ class AdamDesc(C.Structure):
 
 
 _STRUCTS = {0: ConvDesc, 1: PoolDesc, 2: YoloDesc, 3: NmsDesc, 4: HeadsDesc, 5: HeadsWeights, 6: Conv16Desc, 7: PackDesc,
-            8: Bneck16Desc, 9: AdamDesc, 10: RadarDesc, 11: NmsPythonDesc, 12: YoloRectDesc}
+            8: Bneck16Desc, 9: AdamDesc, 10: RadarDesc, 11: NmsPythonDesc, 12: YoloRectDesc, 13: BoxTracksDesc}
 
 # name -> (restype, argtypes); every symbol include/millieye_hip.h declares
 SIGNATURES = {
@@ -248,6 +263,10 @@ SIGNATURES = {
     "me_radar_tracker_state_bytes": (C.c_int64, [C.c_int32]),
     "me_radar_tracker_reset": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "me_radar_proposals_f64": (C.c_int, [C.POINTER(RadarDesc), C.c_void_p]),
+    "me_box_tracks_capacity": (C.c_int32, [C.c_int32]),
+    "me_box_tracks_state_bytes": (C.c_int64, [C.c_int32]),
+    "me_box_tracks_reset": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "me_box_tracks_f64": (C.c_int, [C.POINTER(BoxTracksDesc), C.c_void_p]),
     "me_frame_means_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
     "me_frame_modes_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "me_conv2d_f32": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
@@ -423,6 +442,11 @@ def load(path=None):
     got = tuple(lib_.me_radar_capacity(i) for i in range(len(radar)))
     if got != radar or lib_.me_radar_tracker_state_bytes(1) != RADAR_STATE_HEADER_BYTES + RADAR_TRACK_BYTES * RADAR_MAX_TRACKS:
         raise MeError(f"radar capacities / state layout mismatch: library {got}, binding {radar}")
+    tracks = (TRACKS_MAX_DETS, TRACKS_MAX_TRACKS, TRACKS_ROW_COLS, TRACKS_COUNT_COLS, TRACKS_STATE_HEADER_BYTES,
+              TRACKS_TRACK_BYTES)
+    got = tuple(lib_.me_box_tracks_capacity(i) for i in range(len(tracks)))
+    if got != tracks or lib_.me_box_tracks_state_bytes(1) != TRACKS_STATE_HEADER_BYTES + TRACKS_TRACK_BYTES * TRACKS_MAX_TRACKS:
+        raise MeError(f"box-track capacities / state layout mismatch: library {got}, binding {tracks}")
     _lib = lib_
     return _lib
 
@@ -1066,6 +1090,23 @@ def stream_tail(rows, streams, scalars, iou_threshold):
     (stream in column 0, any order), ``scalars`` [streams,6] float32 CUDA (``utils.utils.rescale_scalars``).  Per stream the second NMS
     and the rescale to its frame, one device-to-host copy for everything.  Returns ``(per_stream, in_counts)``: a list of
     ``[k,7]`` float32 CPU tensors (kept rows in kept order, boxes in frame pixels) and the rows every stream had."""
+    return _stream_tail(rows, streams, scalars, iou_threshold, None)
+
+
+def stream_tail_tracks(rows, streams, scalars, iou_threshold, tracker):
+    """:func:`stream_tail` and, behind it on the same stream, one step of ``tracker``
+    (``detection_tracks.DeviceDetectionTracks``; ``me_box_tracks_f64``): the tracker reads the tail's output buffer where the
+    tail left it on the device, and the tail's words, the tracker's counts and its track rows come to the host in ONE copy -
+    the step has as many copies as :func:`stream_tail`.  Returns ``(per_stream, in_counts, tracks, status)``: the first two are
+    :func:`stream_tail`'s own result; ``tracks`` is a list of ``[k,10]`` float64 numpy arrays (id, x1, y1, x2, y2, conf, cls,
+    hit_streak, age, detection row) and ``status`` the ``TRACKS_*`` word of every stream.  A stream with a status has no track
+    rows and keeps its tracker state; nothing is raised for it."""
+    if tracker.streams != int(streams):
+        raise MeError(f"stream_tail_tracks: the tracker was built for {tracker.streams} streams, the tail has {streams}")
+    return _stream_tail(rows, streams, scalars, iou_threshold, tracker)
+
+
+def _stream_tail(rows, streams, scalars, iou_threshold, tracker):
     _require_cuda_f32(rows, "rows")
     _require_cuda_f32(scalars, "scalars")
     streams = int(streams)
@@ -1079,22 +1120,33 @@ def stream_tail(rows, streams, scalars, iou_threshold):
         nbytes = int(lib().me_stream_tail_out_bytes(streams, m))
         if nbytes != 4 * head + 28 * m:
             raise MeError(f"stream_tail: output layout mismatch (library {nbytes} bytes, binding {4 * head + 28 * m})")
-        out = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        # with a tracker its outputs lie behind the tail's in the same allocation: [tail | counts [S,4] int32 | tracks [S,64,10]]
+        at_counts = (nbytes + 15) & ~15
+        at_tracks = at_counts + 16 * streams
+        total = nbytes if tracker is None else at_tracks + 8 * TRACKS_MAX_TRACKS * TRACKS_ROW_COLS * streams
+        out = torch.empty((total,), dtype=torch.uint8, device=dev)
         ws_ptr, _keep = _workspace(lib().me_nms_workspace_bytes(streams, max(m, 1)), dev)
         check(lib().me_stream_tail_f32(rows.data_ptr(), m, streams, scalars.data_ptr(), float(iou_threshold), out.data_ptr(),
                                        ws_ptr, stream_ptr()), "me_stream_tail_f32")
-        host = out.cpu()   # the one copy: status, counts and the kept rows of every stream
+        if tracker is not None:
+            tracker.launch(out.data_ptr(), m, out.data_ptr() + at_tracks, out.data_ptr() + at_counts)
+        host = out.cpu()   # the one copy: status, counts and the kept rows of every stream (and the tracker's counts and rows)
     ints = host[:4 * head].view(torch.int32)
     if int(ints[0]):
         raise MeError(f"stream_tail: a row's stream column is not an integer in [0, {streams})")
     in_counts = ints[1:1 + streams].tolist()
     kept = ints[1 + streams:1 + 2 * streams].tolist()
-    table = host[4 * head:].view(torch.float32).reshape(m, 7)
+    table = host[4 * head:nbytes].view(torch.float32).reshape(m, 7)
     per_stream, start = [], 0
     for s in range(streams):
         per_stream.append(table[start:start + kept[s]].clone())
         start += in_counts[s]
-    return per_stream, in_counts
+    if tracker is None:
+        return per_stream, in_counts
+    counts = host[at_counts:at_tracks].view(torch.int32).reshape(streams, 4).numpy().copy()
+    table = host[at_tracks:].view(torch.float64).reshape(streams, TRACKS_MAX_TRACKS, TRACKS_ROW_COLS).numpy()
+    tracker.host_counts = counts
+    return per_stream, in_counts, [table[s, :int(counts[s, 1])].copy() for s in range(streams)], counts[:, 0].tolist()
 
 
 def _roi(fn_name, map_nhwc, rois, pooled, spatial_scale, ps):
