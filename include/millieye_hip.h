@@ -996,6 +996,45 @@ int64_t me_box_tracks_state_bytes(int32_t streams);
 int me_box_tracks_reset(void* state, int32_t streams, int32_t which, void* stream);
 int me_box_tracks_f64(const me_box_tracks_desc* d, void* stream);
 
+/* ---- radar range and radial speed for the detections of every stream (csrc/box_ranges.hip) ----------------------------
+ * me_box_ranges_f64: for every kept row of me_stream_tail_f32 the range and the radial speed of the radar returns that
+ *   belong to its box, from the kept points me_radar_proposals_f64 left on the device; one launch behind the tail's, one wave
+ *   per detection row, float64 without contraction, bit-equal to its specification
+ *   millieye_amd/detection_range.py:range_detections.
+ *   tail_out: the device output buffer of me_stream_tail_f32 exactly as that call left it (for `streams` streams and `m` rows);
+ *   cloud_slots [streams, MAX_POINTS, 4] float64 (u, v, range, velocity) in pixels of the stream's frame, ranges and
+ *   velocities finite; radar_counts [streams, 8] int32, column 1 = the kept points of the stream.  No host read-back in between.
+ *   Per kept row (x1, y1, x2, y2, ...), every operation rounded on its own: cx = (x1 + x2) * 0.5, cy likewise,
+ *   hw = ((x2 - x1) * 0.5) * shrink, hh likewise; a point is inside when |u - cx| <= hw and |v - cy| <= hh (a NaN in the box:
+ *   nothing is inside); the n inside points are ordered by (range, cloud index); c_j = the ordered points i >= j with
+ *   r_i <= r_j + gate; the first j with c_j >= min_points gives the group j .. j + c_j - 1, whose ranges and velocities are
+ *   summed left to right in that order and divided by c = c_j.  A point may serve several rows.
+ *   ranges [m, 4] float64, indexed like the tail's table (the kept rows of stream s start at the sum of the rows of the streams
+ *   before s): (range, velocity, c, n), or (NaN, NaN, 0, n) without such a j.  Only kept rows are written; every other byte of
+ *   ranges stays as it was (may be NULL when m = 0).  status [streams] int32: ME_RANGES_OK; ME_RANGES_E_INPUT for every stream,
+ *   and no row written, when tail_out is flagged or its counts are inconsistent with m; ME_RANGES_E_POINTS for a stream whose
+ *   point count is outside [0, MAX_POINTS] - its rows are not written, the other streams are not affected.  The call returns 0
+ *   in all these cases.  m <= 32768, streams <= 65535, min_points >= 1; shrink and gate not NaN. */
+#define ME_RANGES_MAX_POINTS 256   /* = ME_RADAR_MAX_POINTS */
+#define ME_RANGES_ROW_COLS 4
+#define ME_RANGES_COUNT_COLS 8     /* = ME_RADAR_COUNT_COLS: the row length of radar_counts */
+#define ME_RANGES_POINTS_COL 1     /* the column of radar_counts that holds the kept points */
+#define ME_RANGES_OK 0
+#define ME_RANGES_E_INPUT 1    /* tail_out is flagged or inconsistent with m            */
+#define ME_RANGES_E_POINTS 2   /* the stream's point count is outside [0, MAX_POINTS]   */
+typedef struct me_box_ranges_desc {
+  const void* tail_out;
+  const double* cloud_slots;
+  const int32_t* radar_counts;
+  double* ranges;
+  int32_t* status;
+  double shrink, gate;
+  int32_t m, streams, min_points, reserved;
+} me_box_ranges_desc;
+/* which = 0 MAX_POINTS, 1 ROW_COLS, 2 COUNT_COLS, 3 POINTS_COL; -1 otherwise */
+int32_t me_box_ranges_capacity(int32_t which);
+int me_box_ranges_f64(const me_box_ranges_desc* d, void* stream);
+
 /* ---- evaluation tail -----------------------------------------------------------------
  * get_batch_statistics (module3_our_dataset/utils/utils.py:185-236) for one batch, on the output rows of
  * Network.forward as they are: rows [m,cols] = (image_i, x1,y1,x2,y2, ..., class_pred last), targets [q,6] =
@@ -1121,7 +1160,7 @@ int me_adam_step_f32(const me_adam_desc* d, void* stream);
 int32_t me_adam_chunk(void);
 
 /* sizes of the descriptor structs, so a binding can assert its mirror layout */
-int32_t me_sizeof(int32_t which); /* 0 conv, 1 pool, 2 yolo, 3 nms, 4 heads, 5 heads_weights, 6 conv16, 7 pack, 8 bneck16, 9 adam, 10 radar, 11 nms_python, 12 yolo_rect, 13 box_tracks */
+int32_t me_sizeof(int32_t which); /* 0 conv, 1 pool, 2 yolo, 3 nms, 4 heads, 5 heads_weights, 6 conv16, 7 pack, 8 bneck16, 9 adam, 10 radar, 11 nms_python, 12 yolo_rect, 13 box_tracks, 14 box_ranges */
 
 #ifdef __cplusplus
 }

@@ -46,6 +46,7 @@ int32_t me_sizeof(int32_t which) {
     case 11: return (int32_t)sizeof(me_nms_python_desc);
     case 12: return (int32_t)sizeof(me_yolo_rect_desc);
     case 13: return (int32_t)sizeof(me_box_tracks_desc);
+    case 14: return (int32_t)sizeof(me_box_ranges_desc);
     default: return -1;
   }
 }

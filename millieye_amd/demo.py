@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import hip
+from .detection_range import range_detections, ranging_params
 from .radar_proposals import DeviceRadarProposals, RadarProposalGenerator
 from .utils.datasets import (FrameSurface, StagedImages, StagedRadarMaps, StagedRaggedImages, StagedSurfaces, _pad_amounts,
                              picture_hw, pixel_format_names, resize_mode)
@@ -122,10 +123,15 @@ class FrameFuser:
     the rows come back through the per-axis ``rescale_boxes``.  ``(S, S)`` is ``S``; ``resize="area"`` is refused.
 
     ``frame`` may be a ``utils.datasets.FrameSurface`` (a pitched or device-resident picture, read where it lies by
-    ``StagedSurfaces``); its format must be ``pixel_format`` where that is given, and a cropped surface is refused."""
+    ``StagedSurfaces``); its format must be ``pixel_format`` where that is given, and a cropped surface is refused.
+
+    ``ranging``: ``None`` (default), ``True`` or a dict of ``shrink``, ``gate``, ``min_points`` - ``info`` gains ``"ranges"``,
+    the ``[k,4]`` float64 rows ``(range_m, velocity_mps, points_used, points_inside)`` of
+    ``detection_range.range_detections`` on the returned detections and the cloud of the host generator, and
+    ``"range_status"`` (always 0 here), like :class:`MultiStreamFuser`'s."""
 
     def __init__(self, model, calib_param, model_mode=3, img_size=416, nms_iou=0.3, dark_threshold=0.08, generator=None,
-                 pixel_format=None, resize=None, **generator_kwargs):
+                 pixel_format=None, resize=None, ranging=None, **generator_kwargs):
         self.model, self.model_mode, self.img_size = model, model_mode, _network_input_size(img_size, "FrameFuser")
         self.rect = isinstance(self.img_size, tuple)
         self.nms_iou, self.dark_threshold = nms_iou, dark_threshold
@@ -136,6 +142,7 @@ class FrameFuser:
         if self.rect and self.resize == "area":
             raise hip.MeError(f"FrameFuser: resize='area' has no rectangular form (img_size {self.img_size[0]} x "
                               f"{self.img_size[1]})")
+        self.range_params = ranging_params(ranging, "FrameFuser")
         self.generator_is_default = generator is None   # pipeline.py: re-created in the producer vs sent by pickle
         self.generator = generator or RadarProposalGenerator(calib_param, **generator_kwargs)
 
@@ -163,6 +170,7 @@ class FrameFuser:
             img = StagedImages([frame], self.img_size)
         proposals, cloud = self.generator(radar_frames)
         return dict(hw=(h, w), proposals=proposals, points=int(len(cloud)),
+                    cloud=np.array(cloud, dtype=np.float64).reshape(-1, 4),   # for ranging=: whichever fuser infers decides
                     radar_box=radar_boxes_for_network(proposals, (h, w), self.img_size if self.rect else None),
                     img=img, radar_map=StagedRadarMaps([cloud], [(w, h)],
                                                        map_size=_rect_map_size(self.img_size) if self.rect else 32))
@@ -181,8 +189,10 @@ class FrameFuser:
         rows = rows[keep]
         if len(rows):
             rescale_boxes(rows, self.img_size, (h, w))
-        return rows, dict(mode=mode, proposals=payload["proposals"], radar_boxes=int(radar_box.shape[0]),
-                          points=payload["points"])
+        info = dict(mode=mode, proposals=payload["proposals"], radar_boxes=int(radar_box.shape[0]), points=payload["points"])
+        if self.range_params is not None:
+            info.update(ranges=range_detections(rows.numpy(), payload["cloud"], **self.range_params), range_status=0)
+        return rows, info
 
 
 def prepare_streams(frames, radar_frames, streams, img_size=416, pack=False, pixel_format=None, resize=None, out=None):
@@ -314,10 +324,23 @@ class MultiStreamFuser:
     S host trackers take 0.2 - 7.3 ms.  It needs ``tail="device"``.  :attr:`tracker` is the device tracker
     (``tracker.reset(stream)`` forgets one stream's tracks).  :meth:`advance` does not touch it: a step that ``pipeline.FusionPipeline`` skips has no
     detections, so it does not age the tracks - ``max_age`` counts the steps that were inferred, not the frames that
-    arrived."""
+    arrived.
+
+    ``ranging``: ``None`` (default) - nothing below happens.  ``True`` or a dict of ``detection_range.range_detections``
+    parameters (``shrink``, ``gate``, ``min_points``): every detection gets the range and the radial speed of the radar returns
+    inside its box, from the kept points the radar chain left on the device (``detection_range.DeviceDetectionRanges``, one
+    launch behind the tail's and the tracker's, ``me_box_ranges_f64``; ``hip.stream_tail_ranges``) - in every mode, the radar
+    chain runs in camera-only steps too, and with square and rectangular ``img_size``, the tail's rows are frame pixels either
+    way.  Every stream's ``info`` gains ``"ranges"``, a ``[k,4]`` float64 numpy array ``(range_m, velocity_mps, points_used,
+    points_inside)`` with one row per returned detection - ``(NaN, NaN, 0, n)`` where no group of ``min_points`` returns was
+    found - and ``"range_status"`` (0 or a ``hip.RANGES_E_*`` word); with ``tracks=`` as well also ``"track_ranges"``
+    ``[t,4]``: ``ranges[det]`` per track row, ``(NaN, NaN, 0, 0)`` where ``det < 0``.  The rows are bit-equal to
+    ``range_detections(rows, generator.cloud(s))``; the detection rows, the tracks and the device-to-host copies of a step
+    are unchanged.  It needs ``tail="device"``.  Cost: ``profiles/box_ranges_latency.txt``."""
 
     def __init__(self, model, calib_params, streams, model_mode=3, img_size=416, nms_iou=0.3, dark_threshold=0.08,
-                 tail="device", split="forwards", pixel_format=None, resize=None, tracks=None, **generator_kwargs):
+                 tail="device", split="forwards", pixel_format=None, resize=None, tracks=None, ranging=None,
+                 **generator_kwargs):
         self.model, self.model_mode, self.streams = model, model_mode, int(streams)
         self.img_size = _network_input_size(img_size, "MultiStreamFuser")
         self.rect = isinstance(self.img_size, tuple)
@@ -347,8 +370,12 @@ class MultiStreamFuser:
             self.track_params = {} if tracks is True else dict(tracks)
         else:
             self.track_params = None
-        self._tracker = None
+        self.range_params = ranging_params(ranging, "MultiStreamFuser")
+        if self.range_params is not None and tail != "device":
+            raise hip.MeError("MultiStreamFuser: ranging needs tail='device' (the kernel reads the device tail's output buffer)")
+        self._tracker = self._ranger = None
         self._step_tracks = None       # (rows per stream, status per stream) of the step being inferred
+        self._step_ranges = None       # the same for the ranges
         self.calib_params, self.generator_kwargs = calib_params, generator_kwargs
         self._device = getattr(model, "device", None)
         self._generator = None
@@ -374,6 +401,14 @@ class MultiStreamFuser:
             from .detection_tracks import DeviceDetectionTracks
             self._tracker = DeviceDetectionTracks(self.streams, device=self.device, **self.track_params)
         return self._tracker
+
+    @property
+    def ranger(self):
+        """The ``DeviceDetectionRanges`` of ``ranging=`` (built on first use); ``None`` without ranging."""
+        if self._ranger is None and self.range_params is not None:
+            from .detection_range import DeviceDetectionRanges
+            self._ranger = DeviceDetectionRanges(self.streams, device=self.device, **self.range_params)
+        return self._ranger
 
     def __call__(self, frames, radar_frames):
         return self.infer(self.prepare(frames, radar_frames))
@@ -460,7 +495,15 @@ class MultiStreamFuser:
                                    radar_boxes=int(counts[s, 4]), points=int(counts[s, 1]))))
             if self._step_tracks is not None:
                 result[-1][1].update(tracks=self._step_tracks[0][s], track_status=int(self._step_tracks[1][s]))
-        self._step_tracks = None
+            if self._step_ranges is not None:
+                ranges = self._step_ranges[0][s]
+                result[-1][1].update(ranges=ranges, range_status=int(self._step_ranges[1][s]))
+                if self._step_tracks is not None:   # host indexing of what already came back
+                    det = self._step_tracks[0][s][:, 9].astype(np.int64)
+                    track_ranges = np.tile(np.array([np.nan, np.nan, 0.0, 0.0]), (len(det), 1))
+                    track_ranges[det >= 0] = ranges[det[det >= 0]]
+                    result[-1][1]["track_ranges"] = track_ranges
+        self._step_tracks = self._step_ranges = None
         return result
 
     def _tail(self, rows, hws):
@@ -470,6 +513,14 @@ class MultiStreamFuser:
             key = tuple(hws)
             if self._scalars[0] != key:   # the frame sizes rarely change: their scalars stay on the device
                 self._scalars = (key, rescale_scalars(self.img_size, hws).to(rows.device))
+            if self.range_params is not None:
+                gen = self.generator
+                got = hip.stream_tail_ranges(rows.to(torch.float32).contiguous(), self.streams, self._scalars[1], self.nms_iou,
+                                             self.ranger, gen._cloud_slots, gen._counts, tracker=self.tracker)
+                if self.track_params is not None:
+                    self._step_tracks = got[2:4]
+                self._step_ranges = got[-2:]
+                return got[0]
             if self.track_params is not None:
                 per_stream, _counts, tracks, status = hip.stream_tail_tracks(
                     rows.to(torch.float32).contiguous(), self.streams, self._scalars[1], self.nms_iou, self.tracker)

@@ -11,6 +11,7 @@ as ``millieye_amd/libmillieye_hip.so``.
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 __all__ = ["lib", "available", "default_device", "MeError"]
@@ -204,6 +205,20 @@ TRACKS_MAX_DETS, TRACKS_MAX_TRACKS, TRACKS_ROW_COLS, TRACKS_COUNT_COLS = 64, 64,
 TRACKS_STATE_HEADER_BYTES, TRACKS_TRACK_BYTES = 32, 224
 TRACKS_OK, TRACKS_E_DETS, TRACKS_E_INPUT, TRACKS_E_TRACKS = 0, 1, 2, 3   # more than 64 detections / bad input / more than 64 tracks
 
+
+class BoxRangesDesc(C.Structure):
+    """me_box_ranges_desc: radar range and radial speed of every detection behind the stream tail (csrc/box_ranges.hip)."""
+    _fields_ = [(name, C.c_void_p) for name in ("tail_out", "cloud_slots", "radar_counts", "ranges", "status")] + [
+        ("shrink", C.c_double), ("gate", C.c_double),
+        ("m", C.c_int32), ("streams", C.c_int32), ("min_points", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+# capacities / status words of me_box_ranges_f64 (include/millieye_hip.h); load() checks them against the library
+# (me_box_ranges_capacity) and against the radar chain's, whose buffers the kernel reads
+RANGES_MAX_POINTS, RANGES_ROW_COLS, RANGES_COUNT_COLS, RANGES_POINTS_COL = 256, 4, 8, 1
+RANGES_OK, RANGES_E_INPUT, RANGES_E_POINTS = 0, 1, 2   # tail flagged or inconsistent with m / a point count outside [0, 256]
+
 ADAM_MAX_TENSORS = 64
 
 # me_conv_wgrad_form (include/millieye_hip.h): ME_WGRAD_FORM_* / ME_WGRAD_REDUCE_* by name
@@ -228,7 +243,8 @@ class AdamDesc(C.Structure):
 
 
 _STRUCTS = {0: ConvDesc, 1: PoolDesc, 2: YoloDesc, 3: NmsDesc, 4: HeadsDesc, 5: HeadsWeights, 6: Conv16Desc, 7: PackDesc,
-            8: Bneck16Desc, 9: AdamDesc, 10: RadarDesc, 11: NmsPythonDesc, 12: YoloRectDesc, 13: BoxTracksDesc}
+            8: Bneck16Desc, 9: AdamDesc, 10: RadarDesc, 11: NmsPythonDesc, 12: YoloRectDesc, 13: BoxTracksDesc,
+            14: BoxRangesDesc}
 
 # name -> (restype, argtypes); every symbol include/millieye_hip.h declares
 SIGNATURES = {
@@ -267,6 +283,8 @@ SIGNATURES = {
     "me_box_tracks_state_bytes": (C.c_int64, [C.c_int32]),
     "me_box_tracks_reset": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "me_box_tracks_f64": (C.c_int, [C.POINTER(BoxTracksDesc), C.c_void_p]),
+    "me_box_ranges_capacity": (C.c_int32, [C.c_int32]),
+    "me_box_ranges_f64": (C.c_int, [C.POINTER(BoxRangesDesc), C.c_void_p]),
     "me_frame_means_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
     "me_frame_modes_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "me_conv2d_f32": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
@@ -447,6 +465,10 @@ def load(path=None):
     got = tuple(lib_.me_box_tracks_capacity(i) for i in range(len(tracks)))
     if got != tracks or lib_.me_box_tracks_state_bytes(1) != TRACKS_STATE_HEADER_BYTES + TRACKS_TRACK_BYTES * TRACKS_MAX_TRACKS:
         raise MeError(f"box-track capacities / state layout mismatch: library {got}, binding {tracks}")
+    ranges = (RANGES_MAX_POINTS, RANGES_ROW_COLS, RANGES_COUNT_COLS, RANGES_POINTS_COL)
+    got = tuple(lib_.me_box_ranges_capacity(i) for i in range(len(ranges)))
+    if got != ranges or ranges[0] != RADAR_MAX_POINTS or ranges[2] != RADAR_COUNT_COLS:
+        raise MeError(f"box-range capacities mismatch: library {got}, binding {ranges}")
     _lib = lib_
     return _lib
 
@@ -1106,7 +1128,57 @@ def stream_tail_tracks(rows, streams, scalars, iou_threshold, tracker):
     return _stream_tail(rows, streams, scalars, iou_threshold, tracker)
 
 
-def _stream_tail(rows, streams, scalars, iou_threshold, tracker):
+def _require_cuda(t, dtype, shape, name, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
+        raise MeError(f"{what}: {name} must be a contiguous CUDA {dtype} tensor of shape {list(shape)}")
+
+
+def box_ranges(tail_out, m, streams, cloud_slots, radar_counts, ranges_out, status_out, shrink=0.8, gate=1.0, min_points=2):
+    """The bare launch of ``me_box_ranges_f64`` on caller-owned device tensors (asynchronous): ``tail_out`` the uint8 output
+    buffer of ``me_stream_tail_f32`` for ``streams`` streams and ``m`` rows, ``cloud_slots`` [streams,256,4] float64 and
+    ``radar_counts`` [streams,8] int32 as ``DeviceRadarProposals`` keeps them; ``ranges_out`` [m,4] float64 and ``status_out``
+    [streams] int32 are written as include/millieye_hip.h says - only the kept rows, a ``RANGES_*`` word per stream."""
+    m, streams = int(m), int(streams)
+    what = "box_ranges"
+    if streams <= 0 or m < 0:
+        raise MeError(f"{what}: {streams} streams, m = {m}")
+    head = (1 + 2 * streams + 3) & ~3
+    if not isinstance(tail_out, torch.Tensor) or not tail_out.is_cuda or tail_out.dtype != torch.uint8 or tail_out.dim() != 1 \
+            or not tail_out.is_contiguous():
+        raise MeError(f"{what}: tail_out must be a contiguous 1-D CUDA uint8 tensor")
+    if tail_out.numel() < 4 * head + 28 * m:
+        raise MeError(f"{what}: tail_out holds {tail_out.numel()} bytes, {streams} streams and m = {m} need {4 * head + 28 * m}")
+    _require_cuda(cloud_slots, torch.float64, (streams, RANGES_MAX_POINTS, 4), "cloud_slots", what)
+    _require_cuda(radar_counts, torch.int32, (streams, RANGES_COUNT_COLS), "radar_counts", what)
+    _require_cuda(ranges_out, torch.float64, (m, RANGES_ROW_COLS), "ranges_out", what)
+    _require_cuda(status_out, torch.int32, (streams,), "status_out", what)
+    d = BoxRangesDesc()
+    d.tail_out, d.cloud_slots, d.radar_counts = tail_out.data_ptr(), cloud_slots.data_ptr(), radar_counts.data_ptr()
+    d.ranges, d.status = ranges_out.data_ptr() if m else None, status_out.data_ptr()
+    d.shrink, d.gate, d.m, d.streams, d.min_points = float(shrink), float(gate), m, streams, int(min_points)
+    with torch.cuda.device(tail_out.device):
+        check(lib().me_box_ranges_f64(C.byref(d), stream_ptr()), "me_box_ranges_f64")
+
+
+def stream_tail_ranges(rows, streams, scalars, iou_threshold, ranger, cloud_slots, radar_counts, tracker=None):
+    """:func:`stream_tail` (with ``tracker``: :func:`stream_tail_tracks`) and, behind it on the same stream, the radar range and
+    radial speed of every kept row (``ranger``: ``detection_range.DeviceDetectionRanges``; ``me_box_ranges_f64``) from the kept
+    points of the radar chain where they lie (``cloud_slots`` [streams,256,4] float64, ``radar_counts`` [streams,8] int32:
+    ``DeviceRadarProposals._cloud_slots`` / ``._counts``).  The ranges and their status lie behind the tail's block (and the
+    tracker's) in the same allocation, so everything still comes to the host in ONE copy.  Returns the result of
+    :func:`stream_tail` / :func:`stream_tail_tracks` plus ``(ranges, status)``: ``ranges`` a list of ``[k,4]`` float64 numpy
+    arrays ``(range, velocity, points used, points inside)`` aligned with ``per_stream`` and ``status`` the ``RANGES_*`` word
+    of every stream (a stream with ``RANGES_E_POINTS`` has NaN rows; ``RANGES_E_INPUT`` cannot coexist with the tail's own
+    check, which raises)."""
+    streams = int(streams)
+    if ranger.streams != streams or (tracker is not None and tracker.streams != streams):
+        raise MeError(f"stream_tail_ranges: ranger / tracker built for another number of streams than the tail's {streams}")
+    _require_cuda(cloud_slots, torch.float64, (streams, RANGES_MAX_POINTS, 4), "cloud_slots", "stream_tail_ranges")
+    _require_cuda(radar_counts, torch.int32, (streams, RANGES_COUNT_COLS), "radar_counts", "stream_tail_ranges")
+    return _stream_tail(rows, streams, scalars, iou_threshold, tracker, (ranger, cloud_slots, radar_counts))
+
+
+def _stream_tail(rows, streams, scalars, iou_threshold, tracker, ranging=None):
     _require_cuda_f32(rows, "rows")
     _require_cuda_f32(scalars, "scalars")
     streams = int(streams)
@@ -1124,12 +1196,21 @@ def _stream_tail(rows, streams, scalars, iou_threshold, tracker):
         at_counts = (nbytes + 15) & ~15
         at_tracks = at_counts + 16 * streams
         total = nbytes if tracker is None else at_tracks + 8 * TRACKS_MAX_TRACKS * TRACKS_ROW_COLS * streams
+        # with ranging, behind that, each block 16-byte aligned: [ranges [m,4] float64 | status [S] int32]
+        at_ranges = (total + 15) & ~15
+        at_range_status = at_ranges + 8 * RANGES_ROW_COLS * m
+        if ranging is not None:
+            total = at_range_status + 4 * streams
         out = torch.empty((total,), dtype=torch.uint8, device=dev)
         ws_ptr, _keep = _workspace(lib().me_nms_workspace_bytes(streams, max(m, 1)), dev)
         check(lib().me_stream_tail_f32(rows.data_ptr(), m, streams, scalars.data_ptr(), float(iou_threshold), out.data_ptr(),
                                        ws_ptr, stream_ptr()), "me_stream_tail_f32")
         if tracker is not None:
             tracker.launch(out.data_ptr(), m, out.data_ptr() + at_tracks, out.data_ptr() + at_counts)
+        if ranging is not None:
+            ranger, cloud_slots, radar_counts = ranging
+            ranger.launch(out.data_ptr(), m, cloud_slots, radar_counts, out.data_ptr() + at_ranges,
+                          out.data_ptr() + at_range_status)
         host = out.cpu()   # the one copy: status, counts and the kept rows of every stream (and the tracker's counts and rows)
     ints = host[:4 * head].view(torch.int32)
     if int(ints[0]):
@@ -1137,16 +1218,26 @@ def _stream_tail(rows, streams, scalars, iou_threshold, tracker):
     in_counts = ints[1:1 + streams].tolist()
     kept = ints[1 + streams:1 + 2 * streams].tolist()
     table = host[4 * head:nbytes].view(torch.float32).reshape(m, 7)
-    per_stream, start = [], 0
+    per_stream, starts, start = [], [], 0
     for s in range(streams):
         per_stream.append(table[start:start + kept[s]].clone())
+        starts.append(start)
         start += in_counts[s]
-    if tracker is None:
-        return per_stream, in_counts
-    counts = host[at_counts:at_tracks].view(torch.int32).reshape(streams, 4).numpy().copy()
-    table = host[at_tracks:].view(torch.float64).reshape(streams, TRACKS_MAX_TRACKS, TRACKS_ROW_COLS).numpy()
-    tracker.host_counts = counts
-    return per_stream, in_counts, [table[s, :int(counts[s, 1])].copy() for s in range(streams)], counts[:, 0].tolist()
+    result = (per_stream, in_counts)
+    if tracker is not None:
+        counts = host[at_counts:at_tracks].view(torch.int32).reshape(streams, 4).numpy().copy()
+        table = host[at_tracks:at_tracks + 8 * TRACKS_MAX_TRACKS * TRACKS_ROW_COLS * streams].view(torch.float64) \
+            .reshape(streams, TRACKS_MAX_TRACKS, TRACKS_ROW_COLS).numpy()
+        tracker.host_counts = counts
+        result += ([table[s, :int(counts[s, 1])].copy() for s in range(streams)], counts[:, 0].tolist())
+    if ranging is not None:
+        status = host[at_range_status:at_range_status + 4 * streams].view(torch.int32).numpy().copy()
+        table = host[at_ranges:at_range_status].view(torch.float64).reshape(m, RANGES_ROW_COLS).numpy()
+        ranging[0].host_status = status
+        nothing = np.array([[np.nan, np.nan, 0.0, 0.0]])
+        result += ([table[starts[s]:starts[s] + kept[s]].copy() if status[s] == RANGES_OK else np.repeat(nothing, kept[s], 0)
+                    for s in range(streams)], status.tolist())
+    return result
 
 
 def _roi(fn_name, map_nhwc, rois, pooled, spatial_scale, ps):
