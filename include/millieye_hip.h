@@ -1035,6 +1035,74 @@ typedef struct me_box_ranges_desc {
 int32_t me_box_ranges_capacity(int32_t which);
 int me_box_ranges_f64(const me_box_ranges_desc* d, void* stream);
 
+/* ---- boxes and labels painted into every stream's picture (csrc/frame_overlay.hip) -------------------------------------
+ * me_frame_overlay_u8: what the reference's demos do with a result (cv2.rectangle + cv2.putText per kept detection,
+ *   module3_our_dataset/run_mp.py:320-330) for the pictures of `streams` streams in their native pixel formats, where they lie
+ *   in device memory; one launch behind me_stream_tail_f32 (and me_box_tracks_f64 / me_box_ranges_f64), no read-back in between,
+ *   bit-equal to its specification millieye_amd/frame_overlay.py:draw_detections.
+ *   tail_out: the device output buffer of me_stream_tail_f32 exactly as that call left it (for `streams` streams and `m` rows).
+ *   tracks [streams, 64, 10] float64 + track_counts [streams, 4] int32 as me_box_tracks_f64 left them (both NULL: no ids; a
+ *   stream with a tracker status other than 0 has none); ranges [m, 4] float64 + range_status [streams] int32 as
+ *   me_box_ranges_f64 left them (ranges NULL: no ranges; range_status NULL: every stream's rows count; a stream with a status
+ *   other than 0 has none).  surfaces [streams, 10] int64 on the device: the descriptor of me_image_batch_surfaces_u8_f32 (column
+ *   5, flip, is ignored: the rows are pixels of the picture as it lies); surfaces_host: the same rows in host memory.  Every
+ *   host row must keep that entry point's validity rules, else the call returns ME_E_BADARG and nothing is launched (refused,
+ *   not clamped); the kernel applies the rules to the device rows again and gives a stream that fails them
+ *   ME_OVERLAY_E_SURFACE and writes none of its bytes.  The pictures of different streams must not share bytes.
+ *   Items: row i of a stream's kept rows (x1, y1, x2, y2, conf, cls_score, cls) is DRAWN when its coordinates are finite, cls
+ *   is finite with |cls| < 2^31 and class_count < 0 or classes[0 .. class_count) holds k = (int)cls.  A drawn row gives a box
+ *   item and, with ME_OVERLAY_LABELS, a label item, in painter's order box 0, label 0, box 1, ...; every pixel ends with the
+ *   colour of the LAST item that covers it: a pixel of an item is stored only when no later item of the stream covers it, so
+ *   every byte has one writer and the result does not depend on scheduling.  More than ME_OVERLAY_MAX_BOXES drawn rows:
+ *   ME_OVERLAY_E_BOXES for that stream, none of its bytes written.
+ *   Box: corners rint() (half to even) of the float32 values in float64, limited to +-(2^30 + 1024); x2 < x1 or y2 < y1: no
+ *   item at all.  The outline covers [x1,x2] x [y1,y2] (inclusive) without [x1+t, x2-t] x [y1+t, y2-t], t = thickness, clipped
+ *   to the picture.
+ *   Colour: index (k mod palette_len, non-negative), or with ME_OVERLAY_COLOR_BY_TRACK and an id behind the row (id mod
+ *   palette_len); palette [4, palette_len, 3] uint8 = the colours in the stored byte order of ME_PIXFMT_RGB, _BGR, _NV12, _YUYV
+ *   (Y, U, V: Y = ((66R + 129G + 25B + 128) >> 8) + 16, U = ((-38R - 74G + 112B + 128) >> 8) + 128, V = ((112R - 94G - 18B +
+ *   128) >> 8) + 128).  NV12 chroma pair (cx, cy) is written with pixel (2cx, 2cy) by that pixel's owner, a YUYV pair's U, V
+ *   with its even pixel; luma bytes with their own pixel.  Bytes of uncovered pixels, of the row padding and between the
+ *   surfaces are never written.  Byte stores, 64-bit addresses: any offset and pitch.
+ *   Label: "[#<id> ]d.dd[ <r>m]": the id of the first track row with det == i when it lies in [0, 2^31 - 1] (truncated);
+ *   q = clamp(floor(conf * 100 + 0.5), 0, 100) (NaN: 0) as q / 100 . q / 10 % 10 q % 10; with ranges[i][0] finite and
+ *   0 <= d = floor(range * 10 + 0.5) <= 9999, d / 10 . d % 10 m.  float64, no contraction.  glyphs [14, 8] uint8 for
+ *   0-9 . # m space: row r < 7 of a 5 x 7 bitmap, column c in bit 4 - c, at columns 1 .. 5 and rows 1 .. 7 of a 6 x 8 cell,
+ *   every bit font_scale x font_scale pixels.  The plate: 6 font_scale n x 8 font_scale pixels for n characters in the box's
+ *   colour, left edge x1, rows [y1 - 8 font_scale, y1 - 1], or [y1, y1 + 8 font_scale - 1] when y1 - 8 font_scale < 0; glyph
+ *   pixels black when (299R + 587G + 114B) / 1000 >= 128 for the RGB colour, else white; clipped to the picture.
+ *   status [streams] int32.  A set status word of tail_out, or counts inconsistent with m, give every stream
+ *   ME_OVERLAY_E_INPUT and no byte is written.  The call returns 0 in all these cases.  m <= 32768, streams <= 65535,
+ *   thickness 1 .. 8, font_scale 1 .. 4, palette_len 1 .. 256, class_count -1 .. 64. */
+#define ME_OVERLAY_MAX_BOXES 64   /* = ME_TRACKS_MAX_DETS */
+#define ME_OVERLAY_MAX_CHARS 24
+#define ME_OVERLAY_GLYPHS 14
+#define ME_OVERLAY_MAX_PALETTE 256
+#define ME_OVERLAY_MAX_CLASSES 64
+#define ME_OVERLAY_OK 0
+#define ME_OVERLAY_E_BOXES 1     /* more than ME_OVERLAY_MAX_BOXES drawn rows                          */
+#define ME_OVERLAY_E_INPUT 2     /* tail_out is flagged or inconsistent with m                         */
+#define ME_OVERLAY_E_SURFACE 3   /* the stream's device descriptor row fails the surface validity rules */
+#define ME_OVERLAY_LABELS 1           /* flags */
+#define ME_OVERLAY_COLOR_BY_TRACK 2
+typedef struct me_frame_overlay_desc {
+  const void* tail_out;
+  const double* tracks;          /* may be NULL (with track_counts) */
+  const int32_t* track_counts;
+  const double* ranges;          /* may be NULL */
+  const int32_t* range_status;   /* may be NULL */
+  const int64_t* surfaces;       /* device */
+  const int64_t* surfaces_host;  /* host   */
+  const uint8_t* palette;
+  const uint8_t* glyphs;
+  const int32_t* classes;        /* may be NULL when class_count <= 0 */
+  int32_t* status;
+  int32_t m, streams, palette_len, class_count, thickness, font_scale, flags, reserved;
+} me_frame_overlay_desc;
+/* which = 0 MAX_BOXES, 1 MAX_CHARS, 2 GLYPHS, 3 MAX_PALETTE, 4 MAX_CLASSES; -1 otherwise */
+int32_t me_frame_overlay_capacity(int32_t which);
+int me_frame_overlay_u8(const me_frame_overlay_desc* d, void* stream);
+
 /* ---- evaluation tail -----------------------------------------------------------------
  * get_batch_statistics (module3_our_dataset/utils/utils.py:185-236) for one batch, on the output rows of
  * Network.forward as they are: rows [m,cols] = (image_i, x1,y1,x2,y2, ..., class_pred last), targets [q,6] =
@@ -1160,7 +1228,7 @@ int me_adam_step_f32(const me_adam_desc* d, void* stream);
 int32_t me_adam_chunk(void);
 
 /* sizes of the descriptor structs, so a binding can assert its mirror layout */
-int32_t me_sizeof(int32_t which); /* 0 conv, 1 pool, 2 yolo, 3 nms, 4 heads, 5 heads_weights, 6 conv16, 7 pack, 8 bneck16, 9 adam, 10 radar, 11 nms_python, 12 yolo_rect, 13 box_tracks, 14 box_ranges */
+int32_t me_sizeof(int32_t which); /* 0 conv, 1 pool, 2 yolo, 3 nms, 4 heads, 5 heads_weights, 6 conv16, 7 pack, 8 bneck16, 9 adam, 10 radar, 11 nms_python, 12 yolo_rect, 13 box_tracks, 14 box_ranges, 15 frame_overlay */
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,7 @@ int32_t me_sizeof(int32_t which) {
     case 12: return (int32_t)sizeof(me_yolo_rect_desc);
     case 13: return (int32_t)sizeof(me_box_tracks_desc);
     case 14: return (int32_t)sizeof(me_box_ranges_desc);
+    case 15: return (int32_t)sizeof(me_frame_overlay_desc);
     default: return -1;
   }
 }

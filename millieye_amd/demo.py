@@ -30,6 +30,7 @@ import torch
 
 from . import hip
 from .detection_range import range_detections, ranging_params
+from .frame_overlay import dense_frame, draw_detections, overlay_params
 from .radar_proposals import DeviceRadarProposals, RadarProposalGenerator
 from .utils.datasets import (FrameSurface, StagedImages, StagedRadarMaps, StagedRaggedImages, StagedSurfaces, _pad_amounts,
                              picture_hw, pixel_format_names, resize_mode)
@@ -128,10 +129,14 @@ class FrameFuser:
     ``ranging``: ``None`` (default), ``True`` or a dict of ``shrink``, ``gate``, ``min_points`` - ``info`` gains ``"ranges"``,
     the ``[k,4]`` float64 rows ``(range_m, velocity_mps, points_used, points_inside)`` of
     ``detection_range.range_detections`` on the returned detections and the cloud of the host generator, and
-    ``"range_status"`` (always 0 here), like :class:`MultiStreamFuser`'s."""
+    ``"range_status"`` (always 0 here), like :class:`MultiStreamFuser`'s.
+
+    ``overlay``: ``None`` (default), ``True`` or a dict of ``frame_overlay.draw_detections`` style parameters - ``info`` gains
+    ``"overlay"``, a numpy copy of the frame in its native layout with the returned detections (and their ranges, with
+    ``ranging=``) drawn by ``draw_detections`` on the host, and ``"overlay_status"``.  The input frame is not touched."""
 
     def __init__(self, model, calib_param, model_mode=3, img_size=416, nms_iou=0.3, dark_threshold=0.08, generator=None,
-                 pixel_format=None, resize=None, ranging=None, **generator_kwargs):
+                 pixel_format=None, resize=None, ranging=None, overlay=None, **generator_kwargs):
         self.model, self.model_mode, self.img_size = model, model_mode, _network_input_size(img_size, "FrameFuser")
         self.rect = isinstance(self.img_size, tuple)
         self.nms_iou, self.dark_threshold = nms_iou, dark_threshold
@@ -143,6 +148,7 @@ class FrameFuser:
             raise hip.MeError(f"FrameFuser: resize='area' has no rectangular form (img_size {self.img_size[0]} x "
                               f"{self.img_size[1]})")
         self.range_params = ranging_params(ranging, "FrameFuser")
+        self.overlay_params = overlay_params(overlay, "FrameFuser")
         self.generator_is_default = generator is None   # pipeline.py: re-created in the producer vs sent by pickle
         self.generator = generator or RadarProposalGenerator(calib_param, **generator_kwargs)
 
@@ -169,7 +175,13 @@ class FrameFuser:
             h, w = int(frame.shape[0]), int(frame.shape[1])
             img = StagedImages([frame], self.img_size)
         proposals, cloud = self.generator(radar_frames)
-        return dict(hw=(h, w), proposals=proposals, points=int(len(cloud)),
+        canvas = {}
+        if self.overlay_params is not None:   # a copy of the picture in its native layout for infer() to draw on
+            if isinstance(frame, FrameSurface):
+                canvas = dict(canvas=(dense_frame(frame), frame.pixel_format))
+            else:
+                canvas = dict(canvas=(frame.numpy().copy(), self.pixel_format or "rgb"))
+        return dict(hw=(h, w), proposals=proposals, points=int(len(cloud)), **canvas,
                     cloud=np.array(cloud, dtype=np.float64).reshape(-1, 4),   # for ranging=: whichever fuser infers decides
                     radar_box=radar_boxes_for_network(proposals, (h, w), self.img_size if self.rect else None),
                     img=img, radar_map=StagedRadarMaps([cloud], [(w, h)],
@@ -192,6 +204,10 @@ class FrameFuser:
         info = dict(mode=mode, proposals=payload["proposals"], radar_boxes=int(radar_box.shape[0]), points=payload["points"])
         if self.range_params is not None:
             info.update(ranges=range_detections(rows.numpy(), payload["cloud"], **self.range_params), range_status=0)
+        if self.overlay_params is not None:
+            canvas, name = payload["canvas"]
+            status = draw_detections(canvas, name, rows.numpy(), ranges=info.get("ranges"), **self.overlay_params)
+            info.update(overlay=canvas, overlay_status=status)
         return rows, info
 
 
@@ -336,10 +352,23 @@ class MultiStreamFuser:
     found - and ``"range_status"`` (0 or a ``hip.RANGES_E_*`` word); with ``tracks=`` as well also ``"track_ranges"``
     ``[t,4]``: ``ranges[det]`` per track row, ``(NaN, NaN, 0, 0)`` where ``det < 0``.  The rows are bit-equal to
     ``range_detections(rows, generator.cloud(s))``; the detection rows, the tracks and the device-to-host copies of a step
-    are unchanged.  It needs ``tail="device"``.  Cost: ``profiles/box_ranges_latency.txt``."""
+    are unchanged.  It needs ``tail="device"``.  Cost: ``profiles/box_ranges_latency.txt``.
+
+    ``overlay``: ``None`` (default) - nothing below happens.  ``True`` or a dict of ``frame_overlay.draw_detections`` style
+    parameters (``thickness``, ``font_scale``, ``labels``, ``color_by``, ``classes``, ``palette``): every stream's boxes and
+    labels (``#id`` with ``tracks=``, the confidence, the range with ``ranging=``) are painted into its picture on the device
+    (``frame_overlay.DeviceFrameOverlay``, one launch behind the tail's, the tracker's and the ranger's, ``me_frame_overlay_u8``;
+    ``hip.stream_tail_overlay``), bit-equal to ``draw_detections`` on the frame with that step's ``info``.  A stream whose
+    frame is a ``FrameSurface`` on a CUDA buffer is drawn IN PLACE, after the input launch has read it on the same stream; for a
+    frame that came from the host, the uploaded bytes the input launch read are kept and drawn into.  Every stream's ``info``
+    gains ``"overlay"``, a ``FrameSurface`` in device memory (the stream's own surface for an in-place stream), and
+    ``"overlay_status"`` (0 or a ``hip.OVERLAY_E_*`` word: more than 64 drawn rows leave the picture untouched).  The pictures
+    of different streams must not share bytes.  The detection rows, the tracks, the ranges and the device-to-host copies of a
+    step are unchanged (the status words travel in the tail's copy).  It needs ``tail="device"``.  Cost:
+    ``profiles/frame_overlay_latency.txt``."""
 
     def __init__(self, model, calib_params, streams, model_mode=3, img_size=416, nms_iou=0.3, dark_threshold=0.08,
-                 tail="device", split="forwards", pixel_format=None, resize=None, tracks=None, ranging=None,
+                 tail="device", split="forwards", pixel_format=None, resize=None, tracks=None, ranging=None, overlay=None,
                  **generator_kwargs):
         self.model, self.model_mode, self.streams = model, model_mode, int(streams)
         self.img_size = _network_input_size(img_size, "MultiStreamFuser")
@@ -373,6 +402,11 @@ class MultiStreamFuser:
         self.range_params = ranging_params(ranging, "MultiStreamFuser")
         if self.range_params is not None and tail != "device":
             raise hip.MeError("MultiStreamFuser: ranging needs tail='device' (the kernel reads the device tail's output buffer)")
+        self.overlay_params = overlay_params(overlay, "MultiStreamFuser")
+        if self.overlay_params is not None and tail != "device":
+            raise hip.MeError("MultiStreamFuser: overlay needs tail='device' (the kernel reads the device tail's output buffer)")
+        self._painter = None
+        self._step_surfaces = self._step_overlay = None   # the pictures of the step being inferred / their status words
         self._tracker = self._ranger = None
         self._step_tracks = None       # (rows per stream, status per stream) of the step being inferred
         self._step_ranges = None       # the same for the ranges
@@ -409,6 +443,14 @@ class MultiStreamFuser:
             from .detection_range import DeviceDetectionRanges
             self._ranger = DeviceDetectionRanges(self.streams, device=self.device, **self.range_params)
         return self._ranger
+
+    @property
+    def painter(self):
+        """The ``DeviceFrameOverlay`` of ``overlay=`` (built on first use); ``None`` without overlay."""
+        if self._painter is None and self.overlay_params is not None:
+            from .frame_overlay import DeviceFrameOverlay
+            self._painter = DeviceFrameOverlay(self.streams, device=self.device, **self.overlay_params)
+        return self._painter
 
     def __call__(self, frames, radar_frames):
         return self.infer(self.prepare(frames, radar_frames))
@@ -450,6 +492,8 @@ class MultiStreamFuser:
         dev, n = self.device, self.streams
         hws = payload["hw"]
         img = payload["img"].to(dev)
+        if self.overlay_params is not None:   # the pictures in device memory: in place, or the bytes just uploaded
+            self._step_surfaces = payload["img"].device_surfaces()
         step = self.generator.gen(payload["radar_frames"], hws)
         counts = step.host_counts
         if self.rect:   # the resized maps and the per-axis boxes; column 4 becomes the rectangular canvas's count
@@ -503,7 +547,9 @@ class MultiStreamFuser:
                     track_ranges = np.tile(np.array([np.nan, np.nan, 0.0, 0.0]), (len(det), 1))
                     track_ranges[det >= 0] = ranges[det[det >= 0]]
                     result[-1][1]["track_ranges"] = track_ranges
-        self._step_tracks = self._step_ranges = None
+            if self._step_overlay is not None:
+                result[-1][1].update(overlay=self._step_surfaces[s], overlay_status=int(self._step_overlay[s]))
+        self._step_tracks = self._step_ranges = self._step_surfaces = self._step_overlay = None
         return result
 
     def _tail(self, rows, hws):
@@ -513,6 +559,17 @@ class MultiStreamFuser:
             key = tuple(hws)
             if self._scalars[0] != key:   # the frame sizes rarely change: their scalars stay on the device
                 self._scalars = (key, rescale_scalars(self.img_size, hws).to(rows.device))
+            if self.overlay_params is not None:
+                gen = self.generator
+                ranging = None if self.range_params is None else (self.ranger, gen._cloud_slots, gen._counts)
+                got = hip.stream_tail_overlay(rows.to(torch.float32).contiguous(), self.streams, self._scalars[1], self.nms_iou,
+                                              self.painter, self._step_surfaces, tracker=self.tracker, ranging=ranging)
+                if self.track_params is not None:
+                    self._step_tracks = got[2:4]
+                if ranging is not None:
+                    self._step_ranges = got[-3:-1]
+                self._step_overlay = got[-1]
+                return got[0]
             if self.range_params is not None:
                 gen = self.generator
                 got = hip.stream_tail_ranges(rows.to(torch.float32).contiguous(), self.streams, self._scalars[1], self.nms_iou,

@@ -219,6 +219,20 @@ class BoxRangesDesc(C.Structure):
 RANGES_MAX_POINTS, RANGES_ROW_COLS, RANGES_COUNT_COLS, RANGES_POINTS_COL = 256, 4, 8, 1
 RANGES_OK, RANGES_E_INPUT, RANGES_E_POINTS = 0, 1, 2   # tail flagged or inconsistent with m / a point count outside [0, 256]
 
+
+class FrameOverlayDesc(C.Structure):
+    """me_frame_overlay_desc: boxes and labels painted into every stream's picture behind the stream tail (csrc/frame_overlay.hip)."""
+    _fields_ = [(name, C.c_void_p) for name in ("tail_out", "tracks", "track_counts", "ranges", "range_status", "surfaces",
+                                                "surfaces_host", "palette", "glyphs", "classes", "status")] + [
+        (name, C.c_int32) for name in ("m", "streams", "palette_len", "class_count", "thickness", "font_scale", "flags", "reserved")]
+
+
+# capacities / status words / flags of me_frame_overlay_u8 (include/millieye_hip.h); load() checks the capacities against the
+# library (me_frame_overlay_capacity)
+OVERLAY_MAX_BOXES, OVERLAY_MAX_CHARS, OVERLAY_GLYPHS, OVERLAY_MAX_PALETTE, OVERLAY_MAX_CLASSES = 64, 24, 14, 256, 64
+OVERLAY_OK, OVERLAY_E_BOXES, OVERLAY_E_INPUT, OVERLAY_E_SURFACE = 0, 1, 2, 3
+OVERLAY_LABELS, OVERLAY_COLOR_BY_TRACK = 1, 2
+
 ADAM_MAX_TENSORS = 64
 
 # me_conv_wgrad_form (include/millieye_hip.h): ME_WGRAD_FORM_* / ME_WGRAD_REDUCE_* by name
@@ -244,7 +258,7 @@ class AdamDesc(C.Structure):
 
 _STRUCTS = {0: ConvDesc, 1: PoolDesc, 2: YoloDesc, 3: NmsDesc, 4: HeadsDesc, 5: HeadsWeights, 6: Conv16Desc, 7: PackDesc,
             8: Bneck16Desc, 9: AdamDesc, 10: RadarDesc, 11: NmsPythonDesc, 12: YoloRectDesc, 13: BoxTracksDesc,
-            14: BoxRangesDesc}
+            14: BoxRangesDesc, 15: FrameOverlayDesc}
 
 # name -> (restype, argtypes); every symbol include/millieye_hip.h declares
 SIGNATURES = {
@@ -285,6 +299,8 @@ SIGNATURES = {
     "me_box_tracks_f64": (C.c_int, [C.POINTER(BoxTracksDesc), C.c_void_p]),
     "me_box_ranges_capacity": (C.c_int32, [C.c_int32]),
     "me_box_ranges_f64": (C.c_int, [C.POINTER(BoxRangesDesc), C.c_void_p]),
+    "me_frame_overlay_capacity": (C.c_int32, [C.c_int32]),
+    "me_frame_overlay_u8": (C.c_int, [C.POINTER(FrameOverlayDesc), C.c_void_p]),
     "me_frame_means_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
     "me_frame_modes_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "me_conv2d_f32": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
@@ -469,6 +485,10 @@ def load(path=None):
     got = tuple(lib_.me_box_ranges_capacity(i) for i in range(len(ranges)))
     if got != ranges or ranges[0] != RADAR_MAX_POINTS or ranges[2] != RADAR_COUNT_COLS:
         raise MeError(f"box-range capacities mismatch: library {got}, binding {ranges}")
+    overlay = (OVERLAY_MAX_BOXES, OVERLAY_MAX_CHARS, OVERLAY_GLYPHS, OVERLAY_MAX_PALETTE, OVERLAY_MAX_CLASSES)
+    got = tuple(lib_.me_frame_overlay_capacity(i) for i in range(len(overlay)))
+    if got != overlay or overlay[0] != TRACKS_MAX_DETS:
+        raise MeError(f"frame-overlay capacities mismatch: library {got}, binding {overlay}")
     _lib = lib_
     return _lib
 
@@ -1178,7 +1198,85 @@ def stream_tail_ranges(rows, streams, scalars, iou_threshold, ranger, cloud_slot
     return _stream_tail(rows, streams, scalars, iou_threshold, tracker, (ranger, cloud_slots, radar_counts))
 
 
-def _stream_tail(rows, streams, scalars, iou_threshold, tracker, ranging=None):
+def frame_overlay(tail_out, m, streams, surfaces, surfaces_host, palette, glyphs, status_out, tracks=None, ranges=None,
+                  classes=None, class_count=-1, thickness=2, font_scale=1, labels=True, color_by_track=False):
+    """The bare launch of ``me_frame_overlay_u8`` on caller-owned device memory (asynchronous): boxes and labels painted into the
+    pictures ``surfaces`` names.  ``tail_out``: the uint8 output buffer of ``me_stream_tail_f32`` for ``streams`` streams and
+    ``m`` rows (a CUDA tensor, or its address); ``surfaces`` [streams,10] int64 CUDA, the descriptor of
+    ``me_image_batch_surfaces_u8_f32``, and ``surfaces_host`` the same rows as a CPU tensor - checked before the launch, an
+    invalid row raises and nothing is launched; ``palette`` [4,P,3] uint8 and ``glyphs`` [14,8] uint8 CUDA
+    (``frame_overlay.palette_table``, ``frame_overlay.GLYPH_ROWS``); ``status_out`` [streams] int32 CUDA (or its address);
+    ``tracks`` = (tracks [streams,64,10] float64, counts [streams,4] int32) and ``ranges`` = (ranges [m,4] float64, status
+    [streams] int32 or ``None``) as the tracker and the ranger left them on the device (tensors or addresses); ``classes``
+    int32 CUDA with ``class_count`` entries (``-1``: no filter).  Rules: include/millieye_hip.h."""
+    m, streams, what = int(m), int(streams), "frame_overlay"
+    if streams <= 0 or m < 0:
+        raise MeError(f"{what}: {streams} streams, m = {m}")
+
+    def ptr(t):
+        return t if t is None or isinstance(t, int) else t.data_ptr()
+
+    if isinstance(tail_out, torch.Tensor):
+        head = (1 + 2 * streams + 3) & ~3
+        if not tail_out.is_cuda or tail_out.dtype != torch.uint8 or tail_out.dim() != 1 or not tail_out.is_contiguous():
+            raise MeError(f"{what}: tail_out must be a contiguous 1-D CUDA uint8 tensor")
+        if tail_out.numel() < 4 * head + 28 * m:
+            raise MeError(f"{what}: tail_out holds {tail_out.numel()} bytes, {streams} streams and m = {m} need {4 * head + 28 * m}")
+    _require_cuda(surfaces, torch.int64, (streams, 10), "surfaces", what)
+    if not isinstance(surfaces_host, torch.Tensor) or surfaces_host.device.type != "cpu" or surfaces_host.dtype != torch.int64 \
+            or tuple(surfaces_host.shape) != (streams, 10) or not surfaces_host.is_contiguous():
+        raise MeError(f"{what}: surfaces_host must be a contiguous CPU int64 tensor of shape [{streams}, 10]")
+    if not isinstance(palette, torch.Tensor) or palette.dim() != 3 or not 1 <= palette.shape[1] <= OVERLAY_MAX_PALETTE:
+        raise MeError(f"{what}: palette must be a CUDA uint8 tensor [4, 1 .. {OVERLAY_MAX_PALETTE}, 3]")
+    _require_cuda(palette, torch.uint8, (4, int(palette.shape[1]), 3), "palette", what)
+    _require_cuda(glyphs, torch.uint8, (OVERLAY_GLYPHS, 8), "glyphs", what)
+    if isinstance(status_out, torch.Tensor):
+        _require_cuda(status_out, torch.int32, (streams,), "status_out", what)
+    class_count = int(class_count)
+    if class_count > 0:
+        if not isinstance(classes, torch.Tensor) or classes.dim() != 1:
+            raise MeError(f"{what}: classes must be a 1-D CUDA int32 tensor with class_count = {class_count} entries")
+        _require_cuda(classes, torch.int32, (int(classes.shape[0]),), "classes", what)
+        if classes.shape[0] < class_count:
+            raise MeError(f"{what}: classes holds {int(classes.shape[0])} entries, class_count is {class_count}")
+    d = FrameOverlayDesc()
+    d.tail_out, d.surfaces, d.surfaces_host = ptr(tail_out), surfaces.data_ptr(), surfaces_host.data_ptr()
+    d.palette, d.glyphs, d.status = palette.data_ptr(), glyphs.data_ptr(), ptr(status_out)
+    d.classes = ptr(classes) if class_count > 0 else None
+    if tracks is not None:
+        for t, dtype, shape, name in ((tracks[0], torch.float64, (streams, TRACKS_MAX_TRACKS, TRACKS_ROW_COLS), "tracks"),
+                                      (tracks[1], torch.int32, (streams, TRACKS_COUNT_COLS), "track counts")):
+            if isinstance(t, torch.Tensor):
+                _require_cuda(t, dtype, shape, name, what)
+        d.tracks, d.track_counts = ptr(tracks[0]), ptr(tracks[1])
+    if ranges is not None:
+        if isinstance(ranges[0], torch.Tensor):
+            _require_cuda(ranges[0], torch.float64, (m, RANGES_ROW_COLS), "ranges", what)
+        if isinstance(ranges[1], torch.Tensor):
+            _require_cuda(ranges[1], torch.int32, (streams,), "range status", what)
+        d.ranges, d.range_status = ptr(ranges[0]), ptr(ranges[1])
+    d.m, d.streams, d.palette_len, d.class_count = m, streams, int(palette.shape[1]), class_count
+    d.thickness, d.font_scale = int(thickness), int(font_scale)
+    d.flags = (OVERLAY_LABELS if labels else 0) | (OVERLAY_COLOR_BY_TRACK if color_by_track else 0)
+    with torch.cuda.device(surfaces.device):
+        check(lib().me_frame_overlay_u8(C.byref(d), stream_ptr()), "me_frame_overlay_u8")
+
+
+def stream_tail_overlay(rows, streams, scalars, iou_threshold, painter, surfaces, tracker=None, ranging=None):
+    """:func:`stream_tail` (with ``tracker`` / ``ranging`` = ``(ranger, cloud_slots, radar_counts)``: :func:`stream_tail_tracks`
+    / :func:`stream_tail_ranges`) and, behind all of them on the same stream, the boxes and labels of every stream painted into
+    its picture (``painter``: ``frame_overlay.DeviceFrameOverlay``; ``surfaces``: what its ``draw`` takes;
+    ``me_frame_overlay_u8``), reading the tail's, the tracker's and the ranger's rows where they lie.  The painter's status words
+    lie behind everything else in the tail's allocation and come to the host in the same ONE copy.  Returns the result of the
+    tail without overlay plus ``(status,)``: the ``OVERLAY_*`` word of every stream."""
+    streams = int(streams)
+    if painter.streams != streams or (tracker is not None and tracker.streams != streams) \
+            or (ranging is not None and ranging[0].streams != streams):
+        raise MeError(f"stream_tail_overlay: painter / tracker / ranger built for another number of streams than the tail's {streams}")
+    return _stream_tail(rows, streams, scalars, iou_threshold, tracker, ranging, (painter, surfaces))
+
+
+def _stream_tail(rows, streams, scalars, iou_threshold, tracker, ranging=None, overlay=None):
     _require_cuda_f32(rows, "rows")
     _require_cuda_f32(scalars, "scalars")
     streams = int(streams)
@@ -1201,6 +1299,10 @@ def _stream_tail(rows, streams, scalars, iou_threshold, tracker, ranging=None):
         at_range_status = at_ranges + 8 * RANGES_ROW_COLS * m
         if ranging is not None:
             total = at_range_status + 4 * streams
+        # with an overlay, behind everything else: the painter's status [S] int32
+        at_overlay = (total + 15) & ~15
+        if overlay is not None:
+            total = at_overlay + 4 * streams
         out = torch.empty((total,), dtype=torch.uint8, device=dev)
         ws_ptr, _keep = _workspace(lib().me_nms_workspace_bytes(streams, max(m, 1)), dev)
         check(lib().me_stream_tail_f32(rows.data_ptr(), m, streams, scalars.data_ptr(), float(iou_threshold), out.data_ptr(),
@@ -1211,6 +1313,11 @@ def _stream_tail(rows, streams, scalars, iou_threshold, tracker, ranging=None):
             ranger, cloud_slots, radar_counts = ranging
             ranger.launch(out.data_ptr(), m, cloud_slots, radar_counts, out.data_ptr() + at_ranges,
                           out.data_ptr() + at_range_status)
+        if overlay is not None:
+            overlay[0].draw(out, m, overlay[1],
+                            tracker=None if tracker is None else (out.data_ptr() + at_tracks, out.data_ptr() + at_counts),
+                            ranger=None if ranging is None else (out.data_ptr() + at_ranges, out.data_ptr() + at_range_status),
+                            status=out.data_ptr() + at_overlay)
         host = out.cpu()   # the one copy: status, counts and the kept rows of every stream (and the tracker's counts and rows)
     ints = host[:4 * head].view(torch.int32)
     if int(ints[0]):
@@ -1237,6 +1344,8 @@ def _stream_tail(rows, streams, scalars, iou_threshold, tracker, ranging=None):
         nothing = np.array([[np.nan, np.nan, 0.0, 0.0]])
         result += ([table[starts[s]:starts[s] + kept[s]].copy() if status[s] == RANGES_OK else np.repeat(nothing, kept[s], 0)
                     for s in range(streams)], status.tolist())
+    if overlay is not None:
+        result += (host[at_overlay:at_overlay + 4 * streams].view(torch.int32).tolist(),)
     return result
 
 

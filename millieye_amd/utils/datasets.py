@@ -208,6 +208,7 @@ class StagedRaggedImages(StagedImages):
     rect = None            # (H, W) of a rectangular canvas: me_image_batch_letterbox_u8_f32
     ring_slot = None       # set by lend_to_ring(): ``packed`` lies in this slot of a handover.FrameRing and does not pickle
     ring_total = 0         # ... and holds this many bytes
+    uploaded = None        # set by to(): (the packed bytes on the device, the CPU descriptor) of the last upload
 
     def __init__(self, frames, size, flips=None, formats=None, resize=None):
         size = canvas_size(size, "StagedRaggedImages size")
@@ -327,6 +328,7 @@ class StagedRaggedImages(StagedImages):
         total = int(packed.numel())
         d_src = packed.to(device, non_blocking=True)
         d_desc = desc.pin_memory().to(device, non_blocking=True)
+        self.uploaded = (d_src, desc)   # the bytes the launch reads, kept for whoever draws into them (frame_overlay)
         if self.rect:
             hip.check(hip.lib().me_image_batch_letterbox_u8_f32(d_src.data_ptr(), total, d_desc.data_ptr(), n, out.data_ptr(),
                                                                 self.rect[0], self.rect[1], hip.stream_ptr()),
@@ -344,6 +346,14 @@ class StagedRaggedImages(StagedImages):
                                                                    out.data_ptr(), self.size, hip.stream_ptr()),
                   "me_image_batch_pad_resize_flip_u8_f32")
         return out
+
+    def device_surfaces(self):
+        """After :meth:`to`: every frame as a dense :class:`FrameSurface` on the uploaded bytes the input launch read."""
+        if self.uploaded is None:
+            raise hip.MeError("StagedRaggedImages.device_surfaces(): to(device) first")
+        d_src, desc = self.uploaded
+        names = self.formats or ["rgb"] * int(desc.shape[0])
+        return [FrameSurface(d_src, int(desc[i, 1]), int(desc[i, 2]), names[i], int(desc[i, 0])) for i in range(int(desc.shape[0]))]
 
     def type(self, dtype=None, non_blocking=False, **__):
         if dtype is None:
@@ -509,6 +519,7 @@ class StagedSurfaces:
                                   f"{255 * size}")
         self.shape = torch.Size((len(self.surfaces), 3) + canvas_hw(size))
         self.dtype = torch.float32
+        self.uploaded = None   # set by to(): the device copies of the CPU spans of the last upload
 
     def __len__(self):
         return len(self.surfaces)
@@ -557,11 +568,28 @@ class StagedSurfaces:
                 raise hip.MeError(f"StagedSurfaces.to({out.device}): surface {i} lies on {s.buffer.device}")
         spans, _ = self.plan()
         uploads = [buffer[lo:hi].to(device, non_blocking=True) for buffer, lo, hi in spans]
+        self.uploaded = uploads   # the spans the launch reads, kept for whoever draws into them (device_surfaces)
         d_desc = self.descriptor([u.data_ptr() for u in uploads]).pin_memory().to(device, non_blocking=True)
         height, width = canvas_hw(self.size)
         hip.check(hip.lib().me_image_batch_surfaces_u8_f32(d_desc.data_ptr(), n, out.data_ptr(), height, width,
                                                            int(self.resize == "area"), hip.stream_ptr()),
                   "me_image_batch_surfaces_u8_f32")
+        return out
+
+    def device_surfaces(self):
+        """After :meth:`to`: every picture as a :class:`FrameSurface` in device memory - a surface on a CUDA buffer as it is, a
+        surface on a CPU buffer rebased onto the upload of its span (the bytes the input launch read)."""
+        if self.uploaded is None:
+            raise hip.MeError("StagedSurfaces.device_surfaces(): to(device) first")
+        spans, where = self.plan()
+        out = []
+        for s, k in zip(self.surfaces, where):
+            if k is None:
+                out.append(s)
+                continue
+            lo, nv12 = spans[k][1], s.pixel_format == "nv12"
+            out.append(FrameSurface(self.uploaded[k], s.h, s.w, s.pixel_format, s.offset - lo, s.pitch,
+                                    s.uv_offset - lo if nv12 else None, s.uv_pitch if nv12 else None))
         return out
 
     def type(self, dtype=None, non_blocking=False, **__):
